@@ -9,11 +9,17 @@ positions like the reference, and the optimizer updates all 111.5 M optimised pa
     python bench.py                                   # N = 1, BASELINE configs[1] (pre-training, 36 regions + 128 tokens)
     python bench.py --gpus 8 --steps 20 --warmup 5    # spawns 8 ranks itself (torch.distributed.run, RCCL), rank 0 prints
     python bench.py --workload vqa | nlvr2            # BASELINE configs[3] / configs[4] shapes (fine-tuning heads)
+    python bench.py --full                            # + every extra leg and check listed below
+    python bench.py --dump-outputs DIR                # + the last timed step's outputs as DIR/<name>.npy
+
+A plain run sets up, warms up, times --steps steps and prints the result line (metric, value, unit, ms_per_step, ...); nothing
+else runs on the GPU.  --full adds, around and after the timed loop, what the line's extra objects below report (the per-GEMM
+HIP-event profile of the timed steps and the MFMA ceiling measured around them included).
 
 Called under torch.distributed.run (WORLD_SIZE set) it is one rank of that job; called plainly with --gpus N > 1 it
 re-executes itself through `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement); with --full it carries extra objects:
   roofline     -- dominant kernel (the MFMA GEMM instantiation with the largest total time): algorithmic FLOPs per
                   launch / HIP-event duration per launch, against the dense bf16 MFMA peak; `hbm_bound` lists the
                   HBM-bound kernels (LayerNorm, BertAdam, MLM cross-entropy) as GB/s against the 8 TB/s peak
@@ -322,7 +328,7 @@ def parity_side_batch(model, dev, head, T, R, Dv=0):
 def timed_steps(mw, batch, steps, warmup, barrier, profile=True):
     """THE measurement loop (headline and strict mode alike): `warmup` untimed steps, then exactly `steps` steps between
     barrier + synchronize pairs.  -> (wall seconds of the loop, median ms of the per-step HIP events, per-GEMM-kernel HIP-event
-    summary of the timed region or None)."""
+    summary of the timed region or None, what the last timed step returned)."""
     import torch
     from visualbert_amd import ops
     for _ in range(warmup):
@@ -333,15 +339,61 @@ def timed_steps(mw, batch, steps, warmup, barrier, profile=True):
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     t0 = time.perf_counter()
     marks[0].record()
+    out = None
     for i in range(steps):
-        mw.step(batch)
+        out = None                                         # a step's outputs are released before the next step, as when unused
+        out = mw.step(batch)
         marks[i + 1].record()                              # no host sync: the median step time is read after the loop
     barrier()
     elapsed = time.perf_counter() - t0
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(steps))
     median_ms = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
     summ = ops.gemm_profile_stop() if profile else None
-    return elapsed, median_ms, summ
+    return elapsed, median_ms, summ, out
+
+
+DUMP_SAMPLE = 1 << 20          # --dump-outputs: elements kept of a larger output (a fixed, seeded sample); 64 MB in all at most
+DUMP_BUDGET = 64 << 20
+
+
+def dump_outputs(path, out, arena):
+    """--dump-outputs: what the timed path returned in its last step -- ModelWrapper.step's output dict, every tensor and number
+    of it -- plus the parameters that step left (the fp32 arena), as float32 / float64 .npy files under `path`.  An array of more
+    than DUMP_SAMPLE elements is written as `<name>_sample.npy`: the elements at DUMP_SAMPLE flat indices drawn (with
+    replacement) by a generator seeded from the name, so two runs or two builds with the same arguments write the same
+    positions.  The inputs, weights and dropout seeds are the same from run to run and the forward pass is bit-exact from the same
+    state, but the backward pass sums some gradients with fp32 atomics (bias column sums, split-K weight gradients, LayerNorm and
+    embedding reductions) whose order varies: the gradients differ in the last bit between runs, and over the timed steps the
+    optimizer carries that into every dumped array.  -> {file name: shape}."""
+    import zlib
+    import numpy as np
+    import torch
+    arrays = {}
+    for name in sorted(out):
+        v = out[name]
+        if isinstance(v, (int, float)) and not isinstance(v, bool):
+            v = torch.tensor(float(v), dtype=torch.float64)
+        if torch.is_tensor(v):
+            arrays[name] = v.detach()
+    arrays["parameters"] = arena.data.detach()
+    os.makedirs(path, exist_ok=True)
+    written, total = {}, 0
+    for name, t in arrays.items():
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            flat = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g, dtype=torch.int64)
+            idx, rest = [], flat
+            for d in reversed(t.shape):                     # flat index -> one index per dimension (no copy of a strided view)
+                idx.append(rest % d)
+                rest = rest // d
+            t = t[tuple(i.to(t.device) for i in reversed(idx))]
+            name += "_sample"
+        a = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        total += a.nbytes
+        assert total <= DUMP_BUDGET, "--dump-outputs: more than %d bytes" % DUMP_BUDGET
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name + ".npy"] = list(a.shape)
+    return written
 
 
 def traffic_for(key, batch, workload, child_args):
@@ -413,7 +465,7 @@ def strict_mode(dev, head, T, R, Dv, V, batch, steps, warmup, dtype_name, flops_
     mw = ModelWrapper(AttrDict(train_batch_size=batch, learning_rate=5e-5, warmup_proportion=0.1, num_train_epochs=1,
                                gradient_accumulation_steps=1), 1000 * batch, model=model)
     b = synthetic_batch(head, batch, T, R, Dv, V, seed=0, device=dev)
-    elapsed, median_ms, summ = timed_steps(mw, b, steps, warmup, torch.cuda.synchronize, profile=full)
+    elapsed, median_ms, summ, _ = timed_steps(mw, b, steps, warmup, torch.cuda.synchronize, profile=full)
     dt = elapsed / steps
     par = parity_side_batch(model, dev, head, T, R, Dv)
     peak = PEAK_BF16_TFLOPS if dtype_name != "fp32" else PEAK_F32_TFLOPS
@@ -533,7 +585,7 @@ def batch_curve(dev, head, T, R, Dv, V, dtype_name, fps, peak, steps=12, warmup=
         mw = ModelWrapper(AttrDict(train_batch_size=B, learning_rate=5e-5, warmup_proportion=0.1, num_train_epochs=1,
                                    gradient_accumulation_steps=1), (steps + warmup + 20) * B, model=model)
         b = synthetic_batch(head, B, T, R, Dv, V, seed=0, device=dev)
-        _, med, _ = timed_steps(mw, b, steps, warmup, torch.cuda.synchronize, profile=False)
+        _, med, _, _ = timed_steps(mw, b, steps, warmup, torch.cuda.synchronize, profile=False)
         out[B] = dict(ms_per_step=round(med, 3), samples_per_s=round(B / med * 1e3, 1),
                       step_mfu=round(B / med * 1e3 * fps / (peak * 1e12), 4))
         del mw, model, b
@@ -599,6 +651,13 @@ def main():
                     help="skip the short extra leg with the opt-in sparse MLM head (N = 1, pre-training; reported as roofline.value_sparse_mlm_head_optin)")
     ap.add_argument("--no-batch-curve", action="store_true",
                     help="skip the per-GPU batch sweep 8 ... 512 (N = 1, pre-training workload; ~15 s) reported as roofline.batch_curve")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the extra objects of the result line report: per-GEMM profile and roofline, MFMA ceiling, "
+                         "final loss, h2d / sparse-head / vendor legs, parity, strict modes, batch curve, PMC traffic, CPU baseline, "
+                         "replica and all-reduce checks (N > 1); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (and the parameters it left) as "
+                         "DIR/<name>.npy, float32 / float64, a fixed sample of any output larger than 1 M elements (rank 0)")
     ap.add_argument("--selftest-launch", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
 
@@ -687,20 +746,23 @@ def main():
     # the matrix pipes' ceiling on THIS box right before and right after the timed loop (boxes differ by +-3.5 %, a kernel gain of
     # 2 % is invisible in `value` alone): roofline.all_gemm_frac_of_measured_ceiling divides by the mean of the two
     ceil_before = None
-    if dtype == torch.bfloat16 and not args.no_profile:
+    if args.full and dtype == torch.bfloat16 and not args.no_profile:
         for _ in range(min(args.warmup, 3)):
             mw.step(batch)                                     # clocks and caches in the state the loop will see
         ceil_before = measured_mfma_ceiling(dev)
-    elapsed, median_ms, summ = timed_steps(mw, batch, args.steps, args.warmup, barrier, profile=not args.no_profile)
+    elapsed, median_ms, summ, last = timed_steps(mw, batch, args.steps, args.warmup, barrier,
+                                                 profile=args.full and not args.no_profile)
     ceil_after = measured_mfma_ceiling(dev) if ceil_before else None
     et = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if use_dist:
         dist.all_reduce(et, op=dist.ReduceOp.MAX)
     elapsed = float(et.item())
-    loss = float(mw.step(batch)["loss"].detach())
+    dumped = dump_outputs(args.dump_outputs, last, model.bert.arena) if args.dump_outputs and rank == 0 else None
+    last = None
+    loss = float(mw.step(batch)["loss"].detach()) if args.full else None
 
     h2d = None
-    if not args.no_h2d:
+    if args.full and not args.no_h2d:
         stager = FeatureStager(dev)
         host = pin_batch(synthetic_batch(head, B, T, R, Dv, V, seed=rank, device="cpu"))
         nxt, ev = stager.stage(host, 0)
@@ -719,7 +781,7 @@ def main():
 
     allreduce = None
     replicas_same = None
-    if sync is not None:
+    if args.full and sync is not None:
         # replicas must have stayed bit-identical through the synchronised steps: every rank's parameter arena, summed in fp64
         mine = model.bert.arena.data.double().sum().reshape(1)
         sums = [torch.empty_like(mine) for _ in range(world)]
@@ -728,7 +790,7 @@ def main():
         allreduce = sync.measure_allreduce(barrier)             # stand-alone all-reduce of the whole gradient arena
 
     sparse = None
-    if (args.sparse_mlm_head or (world == 1 and not args.no_sparse_leg)) and head == "pretraining":
+    if (args.sparse_mlm_head or (args.full and world == 1 and not args.no_sparse_leg)) and head == "pretraining":
         # the opt-in MLM head over the labelled positions only: the pre-training path never reads the dense fp32
         # logits it materialises (models/model.py:290-297 returns them; ModelWrapper.step uses the loss) -- 20.5 GB of stores per
         # step at B = 1024.  A short extra leg, reported BESIDE `value`, never as `value`: the drop-in contract returns all logits.
@@ -745,7 +807,7 @@ def main():
         mw.model.bert.sparse_mlm_head = False
 
     vendor = None
-    if world == 1 and not args.no_vendor_leg and args.nt_kernel == 0 and args.dtype == "bf16":
+    if args.full and world == 1 and not args.no_vendor_leg and args.nt_kernel == 0 and args.dtype == "bf16":
         # the same step with the PLAIN GEMMs (bias only / "+ addend": 76 of the step's 119) handed to hipBLASLt (nt_kernel 200,
         # csrc/vendor_gemm.hip): what the vendor's hand-scheduled kernel is worth inside the step.  Reported next to `value`,
         # never as `value`: the product path is the hand-written kernels.
@@ -755,7 +817,7 @@ def main():
         if _lib.dev_lib() is not None:
             with _lib.dev_library():
                 _lib.set_opts(nt_kernel=200)
-                tv, _, vs = timed_steps(mw, batch, nv, 3, barrier, profile=True)
+                tv, _, vs, _ = timed_steps(mw, batch, nv, 3, barrier, profile=True)
                 tv /= nv
                 _lib.set_opts(nt_kernel=0)
         lib_ms = sum(v["ms"] for k, v in vs.items() if k & 512) / nv
@@ -801,7 +863,7 @@ def main():
             if dtype == torch.bfloat16:
                 roofline["hbm_bound"] = hbm_bound_kernels(model, B * S, H, dev, optimizer=mw.optimizer,
                                                             V=30522 if head == "pretraining" else 0)
-        if not args.no_parity:
+        if args.full and not args.no_parity:
             par = parity_side_batch(model, dev, head, T, R, Dv)
     # The collective part of the job ends HERE: the communicator and the process group are torn down before rank 0 starts its
     # long host-side legs (strict-mode models, the CPU baseline), so no rank sits in an RCCL barrier under a watchdog meanwhile.
@@ -822,7 +884,7 @@ def main():
             child = ["--workload", args.workload, "--dtype", args.dtype, "--batch", str(B)] + \
                     (["--nt-kernel", str(args.nt_kernel)] if args.nt_kernel else []) + PMC_CHILD_FLAGS
             roofline["traffic"], roofline["traffic_source"] = traffic_for(dominant_key(summ), B, args.workload, child)
-        if world == 1 and args.strict_dtype != "none" and args.dtype == "bf16":
+        if args.full and world == 1 and args.strict_dtype != "none" and args.dtype == "bf16":
             batch = mw = model = None
             torch.cuda.empty_cache()
             kinds = ["bf16x3", "fp32"] if args.strict_dtype == "both" else [args.strict_dtype]
@@ -864,7 +926,7 @@ def main():
                 roofline["batch_curve"] = {str(k): v for k, v in sorted(curve.items())}
                 for k, v in sorted(curve.items()):
                     roofline["batch_curve_b%d_ms" % k] = v["ms_per_step"]
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.cpu_batch, T, R, head)
         metric = {"pretrain": "pretrain samples/sec (BERT-base, 36 regions+128 tok)",
                   "vqa": "VQA2.0 fine-tune samples/sec (BERT-base, 36 regions+20 tok)",
@@ -887,7 +949,7 @@ def main():
             "step_mfu": round(value * fps / (world * peak * 1e12), 4),
             "step_mfu_executed": executed["step_mfu_executed"] if executed else None,
             "executed": executed,
-            "final_loss": round(loss, 4),
+            "final_loss": round(loss, 4) if loss is not None else None,
             "rccl_ranks_seen": ranks_seen,
             "replicas_bit_identical": replicas_same,
             "allreduce": allreduce,
@@ -897,6 +959,8 @@ def main():
             "strict_mode": strict,
             "vendor_plain_gemms": vendor,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dict(dir=args.dump_outputs, arrays=dumped)
         if one_device:
             out["one_device_test_mode"] = "all %d ranks on cuda:0, gloo process group (VB_BENCH_ONE_DEVICE=1)" % world
         if sparse is not None:

@@ -58,10 +58,10 @@ def test_driver_command_ranks_end_to_end(dev, world, batch, extra):
     ranks drive cuda:0 (VB_BENCH_ONE_DEVICE=1; the process group is gloo because RCCL refuses two ranks on one device).
     Everything but the transport is the N > 1 path the scaling bench runs: self-spawn through torch.distributed.run, rank
     environment, per-rank shards, gradient hooks firing during backward, max-over-ranks timing, ONE JSON line from rank 0
-    that still carries cpu_baseline and parity."""
+    that still carries cpu_baseline and parity (--full)."""
     if dev.type != "cuda":
         pytest.skip("needs the GPU")
-    d = _run(["--gpus", str(world), "--batch", str(batch), "--steps", "2", "--warmup", "1", "--cpu-batch", "1", "--no-h2d"] + extra,
+    d = _run(["--gpus", str(world), "--batch", str(batch), "--steps", "2", "--warmup", "1", "--full", "--cpu-batch", "1", "--no-h2d"] + extra,
              extra_env={"VB_BENCH_ONE_DEVICE": "1", "VB_BENCH_HANG_DUMP": "300"}, timeout=240 if world == 2 else 600)
     assert d["n_gpus"] == world and d["rccl_ranks_seen"] == world
     assert d["config"]["global_batch"] == world * batch and d["config"]["parallelism"] == "dp%d" % world
@@ -73,6 +73,59 @@ def test_driver_command_ranks_end_to_end(dev, world, batch, extra):
     assert d["parity"] and d["parity"]["max_dlogit_vs_fp32_ref"] < 0.1
     assert d["value"] > 0 and d["final_loss"] == d["final_loss"]
     assert 5.0 < d["final_loss"] < 15.0                             # ~ln(30522) + ln 2 after three steps from random weights
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_one(dev, tmp_path):
+    """The benchmark as it is run for every change: `--gpus 1 --steps N --warmup W` times exactly N steps, prints the headline
+    fields and none of the --full legs; --dump-outputs writes the last timed step's outputs, the same arrays on a second run."""
+    if dev.type != "cuda":
+        pytest.skip("needs the GPU")
+    import numpy as np
+    runs = []
+    for k in range(2):
+        d = _run(["--gpus", "1", "--batch", "8", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / str(k))])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "bf16" and d["higher_is_better"] is True
+        assert d["ms_per_step"] > 0 and abs(d["value"] - 8 * 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["strict_mode"] is None and d["parity"] is None
+        runs.append(d["dumped_outputs"]["arrays"])
+    assert runs[0] == runs[1] and {"loss.npy", "logits_sample.npy", "parameters_sample.npy"} <= set(runs[0])
+    for name in runs[0]:
+        a, b = np.load(str(tmp_path / "0" / name)), np.load(str(tmp_path / "1" / name))
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all() and a.shape == b.shape, name
+    loss = float(np.load(str(tmp_path / "0" / "loss.npy")))
+    assert 5.0 < loss < 15.0                                        # MLM + ITM from random weights after five steps
+
+
+def test_dump_outputs_writes_fixed_samples(tmp_path):
+    """--dump-outputs on a synthetic output dict (no GPU): small arrays whole, large ones (strided views included) as the same
+    seeded sample on every call, float32 / float64 only, within the 64 MB budget."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+
+    class Arena(object):
+        data = torch.randn(3 << 20)
+
+    logits = torch.randn(16, 40, 2100)[:, :, :2000]                 # 1.28 M elements, not contiguous
+    out = {"logits": logits, "loss": torch.tensor(3.5), "seq_relationship_score": torch.randn(16, 2), "accuracy": 0.25,
+           "cnn_regularization_loss": None, "mask": torch.ones(4, dtype=torch.bool)}
+    w0 = bench.dump_outputs(str(tmp_path / "a"), out, Arena)
+    w1 = bench.dump_outputs(str(tmp_path / "b"), out, Arena)
+    assert w0 == w1 and set(w0) == {"logits_sample.npy", "loss.npy", "seq_relationship_score.npy", "accuracy.npy", "mask.npy",
+                                    "parameters_sample.npy"}
+    total = 0
+    for name in w0:
+        a, b = np.load(str(tmp_path / "a" / name)), np.load(str(tmp_path / "b" / name))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert w0["logits_sample.npy"] == [bench.DUMP_SAMPLE]
+    lg = np.load(str(tmp_path / "a" / "logits_sample.npy"))
+    assert np.isin(lg, logits.numpy()).all()                        # sampled elements, not a copy of something else
+    assert np.array_equal(np.load(str(tmp_path / "a" / "seq_relationship_score.npy")), out["seq_relationship_score"].numpy())
+    assert np.load(str(tmp_path / "a" / "accuracy.npy")).dtype == np.float64
 
 
 def test_pmc_kernel_name_matcher():

@@ -2,8 +2,9 @@
 ModelWrapper.read_and_insert_args (visualbert/models/model_wrapper.py:235-244, train.py:87,200) drop in unchanged.
 
 CPU-only: models are constructed on the meta-free CPU path (no kernel runs); BERT-base construction is ~0.5 GB and a few seconds.
-The reference's own config files are read where they lie when /root/reference exists (this container); a config written for
-this repository in the same commented-JSON format is always tested."""
+The reference's own config files are stored as data fixtures under tests/golden/reference_configs/<task>/ (byte for byte as
+the reference ships them in visualbert/configs/); a config written for this repository in the same commented-JSON format is
+tested as well."""
 import argparse
 import glob
 import os
@@ -17,7 +18,7 @@ from visualbert_amd.optimization import BertAdam
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SAMPLE = os.path.join(HERE, "configs", "sample-coco-pre-train.json")
-REF_CONFIGS = "/root/reference/visualbert/configs"
+REF_CONFIGS = os.path.join(HERE, "golden", "reference_configs")
 
 
 def _cli(**kw):
@@ -101,10 +102,11 @@ def test_sample_config_constructs_model_and_optimizer():
 
 
 def _reference_configs():
-    return sorted(glob.glob(os.path.join(REF_CONFIGS, "*", "*.json")))
+    paths = sorted(glob.glob(os.path.join(REF_CONFIGS, "*", "*.json")))
+    assert len(paths) == 13, paths                         # flickr 3, nlvr2 3, vcr 4, vqa 3
+    return paths
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CONFIGS), reason="the reference tree is not on this machine")
 @pytest.mark.parametrize("path", _reference_configs(), ids=lambda p: "/".join(p.split("/")[-2:]))
 def test_reference_configs_drop_in(path):
     """every config the reference ships: read by read_and_insert_args, and -- for the model type this package builds -- model +
