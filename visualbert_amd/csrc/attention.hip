@@ -1068,22 +1068,25 @@ VB_KERNEL VB_LAUNCH_BOUNDS(NT) attn_bwd_dkv_kernel(AttnArgs a) {
 // =================================================================================================
 // backward in ONE pass (bf16, S <= 192, needs the forward output O = ctx): the two-pass form above computes every
 // score, probability and dP twice (once per pass) and its dQ pass alone is 45 % of the backward time -- per-probability
-// VALU work, not MFMAs, bounds these kernels.  Here one workgroup of 12 waves owns a (batch, head).  Per chunk of 64 queries:
-//   phase A  wave w owns key fragment w exactly like the dK/dV pass (lane <-> key): S, P, dP, dS once; dV^T += dO^T P,
-//            dK^T += Q^T dS; its dS fragment is also written to a [64 queries][192 keys] tile in LDS.
-//            D = rowsum(P o dP) comes from dO . O (same value, dropout included: O = P_drop V), computed while staging.
-//   phase B  the 16 (query fragment, d block) outputs of dQ = dS K for the chunk are split over the waves: full-depth MFMAs
-//            with dS from the tile and K^T from an LDS image built once per (batch, head) -- no atomics, no second exp.
+// VALU work, not MFMAs, bounds these kernels.  Here one workgroup of 4 waves owns a (batch, head); wave w owns the key
+// fragments w, w + 4, w + 8 (lane <-> key, like the dK/dV pass).  Per chunk of 32 queries:
+//   phase A  per owned fragment: S, P, dP, dS once; dV^T += dO^T P, dK^T += Q^T dS; the dS fragment is also written to a
+//            [32 queries][192 keys] tile in LDS.  The chunk's Q / dO A-operands are read from LDS once and feed all three
+//            fragments.  D = rowsum(P o dP) comes from dO . O (same value, dropout included: O = P_drop V), computed while staging.
+//   phase B  the 8 (query fragment, d block) outputs of dQ = dS K for the chunk: wave w owns d block w of both query
+//            fragments (one K^T fragment feeds two MFMA chains), full-depth MFMAs with dS from the tile and K^T from an LDS
+//            image built once per (batch, head) -- no atomics, no second exp.
 // (A first version added per-wave dQ partials into an LDS tile with ds_add_f32: 7x slower than two passes.)
-// Round 5, measured and removed (profiles/r05_attn_bench_b1024_prefetch_ab.txt): an L2 prefetch of the lines workgroup b + 256 (same XCD)
-// opens with, issued by this workgroup once its own fetches were consumed -- 845 -> 907 us alone, 956 -> 1015 us in the step: the four
-// registers it cost spilled (the kernel sits at 168), and scratch reloads wait on vmcnt.  Also measured and removed
-// (profiles/r05_attn_persistent_ab.txt; the kernel is in the git history): the PERSISTENT form -- one workgroup per CU walking the pairs,
-// the next pair's K / V fragments, mask and chunk 0 fetched into registers that are dead by then and its K rows into spare LDS by
-// LDS-direct copies, under the current pair's last phase B and epilogue.  Bit-identical, no VGPR spill after five compiler
-// work-arounds, and at best PARITY: 862 against 853 us.
+// Sized for TWO resident workgroups per CU: 73 KB of LDS (two chunk sets of 18.3 KB, the 24.5 KB K^T image, the 12.3 KB dS
+// tile) and at most 256 VGPRs per wave, one wave of each workgroup per SIMD -- one workgroup's prologue (first HBM round trip,
+// K^T image), epilogue (dK / dV stores, bias-gradient sums) and barrier waits run under the other's phases A and B.  The
+// form it replaces (12 waves, one fragment each, 64-query chunks: 124 KB and 3 x 168 VGPRs per SIMD, ONE workgroup per CU)
+// left the CU's pipes idle through all of those; the same MFMAs in the same order give bit-identical dQ / dK / dV.
+// Round 5, measured and removed on that form (profiles/r05_attn_bench_b1024_prefetch_ab.txt, r05_attn_persistent_ab.txt; the
+// kernels are in the git history): an L2 prefetch of a later workgroup's lines and a PERSISTENT walk of the pairs -- at best parity.
 // =================================================================================================
-constexpr int FWPB = 12, FNT = FWPB * 64, FNK = FWPB * 16;  // 192 keys
+constexpr int RWV = 4, RNT = RWV * 64, RKPW = 3, RCQ = 32;  // waves, threads, key fragments per wave, queries per chunk
+constexpr int FNK = RWV * RKPW * 16;                        // 192 keys
 // Pitches of the two LDS tiles phase B reads: rows of FNK keys + VB_ATTN_BPAD bytes (see LT<bf16>::TPAD above for the round-6
 // experiment with 16: it lost)
 #ifndef VB_ATTN_BPAD
@@ -1092,17 +1095,21 @@ constexpr int FWPB = 12, FNT = FWPB * 64, FNK = FWPB * 16;  // 192 keys
 constexpr int TSP = FNK * 2 + VB_ATTN_BPAD;                // dS tile pitch in bytes (pad: 16 rows -> distinct banks)
 constexpr int KTP = FNK * 2 + VB_ATTN_BPAD;                // K^T image pitch in bytes
 constexpr int KT_BYTES = D * KTP;
+// one chunk set: Q, dO row-major and transposed, lse, D, keep words [CQ][4][NW]
+template <int NKF> constexpr int resident_setb() {
+    return 2 * rm_bytes<bf16>(RCQ) + 2 * tr_bytes<bf16>(RCQ) + 2 * RCQ * 4 + RCQ * 4 * ((NKF + 15) / 16) * 8;
+}
 
-template <int NKF, int CQ>
-VB_KERNEL VB_LAUNCH_BOUNDS(FNT) attn_bwd_fused_kernel(AttnArgs a) {
+template <int NKF>
+VB_KERNEL VB_LAUNCH_BOUNDS2(RNT, 2) attn_bwd_resident_kernel(AttnArgs a) {
     typedef bf16 T;
-    constexpr int NW = (NKF + 15) / 16;
+    constexpr int NW = (NKF + 15) / 16, CQ = RCQ, SETB = resident_setb<NKF>();
+    static_assert(NW == 1, "one keep word per (query, key group): NKF <= 16");
     VB_DYN_SMEM(smem);
     // two sets of chunk images: chunk c+1 is written to LDS while the slower waves still compute on chunk c
-    constexpr int SETB = 2 * rm_bytes<T>(CQ) + 2 * tr_bytes<T>(CQ) + 2 * CQ * 4 + CQ * 4 * NW * 8;
     unsigned char *ldsQ, *ldsDO, *ldsQT, *ldsDOT;
     float *ldsLse, *ldsD;
-    uint64_t* ldsBits;                                     // [CQ][4][NW]
+    uint64_t* ldsBits;
     auto use_set = [&](int set) {
         ldsQ = smem + set * SETB;
         ldsDO = ldsQ + rm_bytes<T>(CQ);
@@ -1114,7 +1121,7 @@ VB_KERNEL VB_LAUNCH_BOUNDS(FNT) attn_bwd_fused_kernel(AttnArgs a) {
     };
     unsigned char* ldsKT = smem + 2 * SETB;                // K^T of the whole sequence: [64 d][FNK keys]
     unsigned char* ldsDS = ldsKT + KT_BYTES;               // dS of the chunk: [CQ queries][FNK keys], pitch TSP
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 15, lg = lane >> 4;
+    const int t = threadIdx.x, lane = t & 63, wave = vb_uniform(t >> 6), li = lane & 15, lg = lane >> 4;
     const int bh = blockIdx.x, b = bh / a.nh, h = bh % a.nh;
     const int S = a.S, H = a.nh * D;
     const long ldx = 3L * H, row0 = (long)b * S;
@@ -1124,63 +1131,66 @@ VB_KERNEL VB_LAUNCH_BOUNDS(FNT) attn_bwd_fused_kernel(AttnArgs a) {
 
     // Every global load below is UNCONDITIONAL from a clamped (always readable) row, and the zero / -inf / all-ones fill of the
     // rows past S is a select at the point of use: the loads carry no branches, nothing waits between them, and a chunk's
-    // fetch really runs a chunk ahead (with `ok ? load : fill` the compiler put s_waitcnt vmcnt(0) between the loads of the
-    // "prefetch" -- the registers' fill is a write-after-write on a pending load -- and the workgroup, alone on its compute
-    // unit, sat through four HBM round trips before its first MFMA and one more per chunk).
-    const int kf = wave;
-    const int key = kf * 16 + li;
-    const bool wave_on = kf * 16 < S;                      // wave-uniform
-    const bool kok = key < S;
-    const int keyc = kok ? key : S - 1;
-    // K^T image source: one row pair x 16-byte chunk per thread (96 pairs x 8 chunks = 768 items = FNT)
-    const int kdc = t & 7, kr = (t >> 3) * 2;
-    const u32x4 kx0 = *(const u32x4*)(qkv + (row0 + (kr < S ? kr : S - 1)) * ldx + H + h * D + kdc * 8);
-    const u32x4 kx1 = *(const u32x4*)(qkv + (row0 + (kr + 1 < S ? kr + 1 : S - 1)) * ldx + H + h * D + kdc * 8);
-    const T* krow = qkv + (row0 + keyc) * ldx + H + h * D;
-    const T* vrow = qkv + (row0 + keyc) * ldx + 2 * H + h * D;
-    bf16x8 kb[2], vb[2];
-    kb[0] = frag_g(krow, 0, lg, kok); kb[1] = frag_g(krow, 1, lg, kok);
-    vb[0] = frag_g(vrow, 0, lg, kok); vb[1] = frag_g(vrow, 1, lg, kok);
-    const float mk_raw = a.mask_add[(long)b * S + keyc];
-    f32x4 dkT[4], dvT[4];
+    // fetch really runs a chunk ahead (with `ok ? load : fill` the compiler puts s_waitcnt vmcnt(0) between the loads of the
+    // "prefetch" -- the registers' fill is a write-after-write on a pending load).
+    // K^T image source: three row pairs x 16-byte chunks per thread (96 pairs x 8 chunks = 768 items = 3 x RNT)
+    constexpr int KTI = (FNK / 2) * 8 / RNT;
+    u32x4 kx0[KTI], kx1[KTI];
 #pragma unroll
-    for (int df = 0; df < 4; ++df) { dkT[df] = f32x4{0.f, 0.f, 0.f, 0.f}; dvT[df] = dkT[df]; }
+    for (int i = 0; i < KTI; ++i) {
+        const int it = t + i * RNT, kdc = it & 7, kr = (it >> 3) * 2;
+        kx0[i] = *(const u32x4*)(qkv + (row0 + (kr < S ? kr : S - 1)) * ldx + H + h * D + kdc * 8);
+        kx1[i] = *(const u32x4*)(qkv + (row0 + (kr + 1 < S ? kr + 1 : S - 1)) * ldx + H + h * D + kdc * 8);
+    }
+    // this wave's key fragments kf = wave + 4 j (interleaved: at S = 100 every wave owns one or two real fragments)
+    bf16x8 kb[RKPW][2], vb[RKPW][2];
+    float mk_raw[RKPW];
+#pragma unroll
+    for (int j = 0; j < RKPW; ++j) {
+        const int key = (wave + RWV * j) * 16 + li;
+        const bool kok = key < S;
+        const int keyc = kok ? key : S - 1;
+        const T* krow = qkv + (row0 + keyc) * ldx + H + h * D;
+        const T* vrow = qkv + (row0 + keyc) * ldx + 2 * H + h * D;
+        kb[j][0] = frag_g(krow, 0, lg, kok); kb[j][1] = frag_g(krow, 1, lg, kok);
+        vb[j][0] = frag_g(vrow, 0, lg, kok); vb[j][1] = frag_g(vrow, 1, lg, kok);
+        mk_raw[j] = a.mask_add[(long)b * S + keyc];
+    }
+    f32x4 dkT[RKPW][4], dvT[RKPW][4];
+#pragma unroll
+    for (int j = 0; j < RKPW; ++j)
+#pragma unroll
+        for (int df = 0; df < 4; ++df) { dkT[j][df] = f32x4{0.f, 0.f, 0.f, 0.f}; dvT[j][df] = dkT[j][df]; }
 
-    constexpr int BPT = (CQ * 4 * NW + FNT - 1) / FNT;
     constexpr int SI = CQ * 4;                             // staging items per tensor (row pair x 16-byte chunk)
-    static_assert(SI % 64 == 0 && CQ == 64, "the staging role must be wave-uniform; wave 0 carries the chunk's lse values");
-    // staging roles (wave-uniform): role 0 (waves 0-3) fetches dO and O for D = dO . O and carries the chunk's lse and keep-bit
-    // words, role 1 (waves 4-7) stages dO, role 2 (waves 8-11) stages Q.  The heaviest staging goes to the OLDEST waves: the
-    // SIMD arbiter favours them in phase A (an in-kernel cycle trace shows waves 0-3 done with a chunk's phase A after ~3700
-    // cycles, waves 8-11 after ~6000 -- three waves per SIMD share its VALU), so they have the slack.
+    static_assert(2 * SI == RNT && CQ * 4 * NW == SI, "two staging roles of 128 threads; one keep word per role-1 thread");
+    // staging roles (wave-uniform): role 0 (waves 0-1) fetches dO and O, stages dO and forms D = dO . O; role 1 (waves 2-3)
+    // stages Q and carries the chunk's lse values and keep-bit words
     const int st = t % SI, role = vb_uniform(t / SI);
     const int sdc = st & 7, sr = (st >> 3) * 2;            // rows q0 + sr, q0 + sr + 1; 16-byte column chunk sdc
     // addresses: byte offsets of this thread's row q0 = 0 from wave-uniform bases, 32 bits (launcher: tokens x pitch x 2 below
     // 2^32); a chunk adds a small signed multiple of the pitch, which also expresses the clamp of rows past S
-    const unsigned char* sbase = (const unsigned char*)((role == 2 ? qkv : dctx) + h * D);   // Q rows | dO rows (roles 0 and 1)
-    const int sldb = (int)((role == 2 ? ldx : (long)H) * 2);                 // row pitch in bytes
+    const unsigned char* sbase = (const unsigned char*)((role == 1 ? qkv : dctx) + h * D);   // Q rows | dO rows
+    const int sldb = (int)((role == 1 ? ldx : (long)H) * 2);                 // row pitch in bytes
     const unsigned char* obase = (const unsigned char*)(octx + h * D);       // O rows: same pitch and offsets as dO
     const unsigned off_s = (unsigned)((row0 + sr) * (long)sldb) + sdc * 16;
+    // role 0: dO rows in c0 / c1, O rows in o0 / o1; role 1: Q rows in c0 / c1, lse and the keep word in o0 (one register set)
     u32x4 c0 = u32x4{0u, 0u, 0u, 0u}, c1 = c0, o0 = c0, o1 = c0;
-    float c_lse = 0.f;
-    uint64_t c_bits[BPT];
-#pragma unroll
-    for (int j = 0; j < BPT; ++j) c_bits[j] = 0;
-    static_assert(BPT == 1 && CQ * 4 * NW == SI, "keep-bit words of a chunk: one per thread of waves 0-3");
     auto load_chunk = [&](int q0) {
         // rows q0 + sr (+ 1), clamped to S - 1, as a row delta from this thread's chunk-0 row sr
         const int d0r = q0 + sr < S ? q0 : S - 1 - sr, d1r = q0 + sr + 1 < S ? q0 + 1 : S - 1 - sr;
-        // ONE pair of loads for every role (role 0 reads the same dO rows as role 1): two branches filling the same registers
-        // made the compiler put a vmcnt wait in front of the second branch's loads
         c0 = *(const u32x4*)(sbase + (off_s + (unsigned)(d0r * sldb)));
         c1 = *(const u32x4*)(sbase + (off_s + (unsigned)(d1r * sldb)));
         if (role == 0) {                                   // wave-uniform: a scalar branch
             o0 = *(const u32x4*)(obase + (off_s + (unsigned)(d0r * sldb)));
             o1 = *(const u32x4*)(obase + (off_s + (unsigned)(d1r * sldb)));
-            if (wave == 0) c_lse = a.lse[(long)bh * S + (q0 + lane < S ? q0 + lane : S - 1)];      // CQ = 64 queries = one wave
+        } else {
+            const int ql = q0 + (st & (CQ - 1));
+            o0[0] = __builtin_bit_cast(uint32_t, a.lse[(long)bh * S + (ql < S ? ql : S - 1)]);
             if (a.p > 0.f) {
-                const long i = ((long)bh * S + q0) * 4 * NW + t, last = ((long)bh * S + S) * 4 * NW - 1;
-                c_bits[0] = a.keepbits[i < last ? i : last];
+                const long i = ((long)bh * S + q0) * 4 * NW + st, last = ((long)bh * S + S) * 4 * NW - 1;
+                const uint64_t w = a.keepbits[i < last ? i : last];
+                o0[2] = (uint32_t)w; o0[3] = (uint32_t)(w >> 32);      // an aligned register pair: loaded in place, no wait
             }
         }
     };
@@ -1196,46 +1206,48 @@ VB_KERNEL VB_LAUNCH_BOUNDS(FNT) attn_bwd_fused_kernel(AttnArgs a) {
     auto store_chunk = [&](int q0) {
         // the fetched registers are consumed from here on, not earlier (the compiler would hoist the selects and the
         // D products -- and with them the wait for the fetch -- above the phase the fetch is supposed to run under)
-        vb_pin(c0); vb_pin(c1); vb_pin(o0); vb_pin(o1); vb_pin(c_lse);
-#pragma unroll
-        for (int j = 0; j < BPT; ++j) vb_pin(c_bits[j]);
+        vb_pin(c0); vb_pin(c1); vb_pin(o0); vb_pin(o1);
         const u32x4 z0 = zsel(q0 + sr < S, c0), z1 = zsel(q0 + sr + 1 < S, c1);        // rows past S are zeros
-        if (role > 0) {
-            unsigned char* rm = role == 2 ? ldsQ : ldsDO;
-            *(u32x4*)(rm + rm_off<T>(sr, sdc)) = z0;
-            *(u32x4*)(rm + rm_off<T>(sr + 1, sdc)) = z1;
-            store_tr2(role == 2 ? ldsQT : ldsDOT, z0, z1);
-        } else {                                           // D[q] = dO[q] . O[q]: 8 products per thread, 8 threads per row
+        unsigned char* rm = role == 1 ? ldsQ : ldsDO;
+        *(u32x4*)(rm + rm_off<T>(sr, sdc)) = z0;
+        *(u32x4*)(rm + rm_off<T>(sr + 1, sdc)) = z1;
+        store_tr2(role == 1 ? ldsQT : ldsDOT, z0, z1);
+        if (role == 0) {                                   // D[q] = dO[q] . O[q]: 8 products per thread, 8 threads per row
             const bf16x8 d0 = *(const bf16x8*)&z0, d1 = *(const bf16x8*)&z1, p0 = *(const bf16x8*)&o0, p1 = *(const bf16x8*)&o1;
             float s0 = 0.f, s1 = 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) { s0 += (float)d0[j] * (float)p0[j]; s1 += (float)d1[j] * (float)p1[j]; }
             s0 = oct_sum(s0); s1 = oct_sum(s1);
             if (sdc == 0) { ldsD[sr] = s0; ldsD[sr + 1] = s1; }
+        } else {
             // lse in units of log 2 (phase A computes exp2 of one packed fma); exp2(x - inf) = 0 for padded queries
-            if (wave == 0) ldsLse[lane] = q0 + lane < S ? c_lse * 1.44269504088896340736f : INFINITY;
-            // keep words, re-laid for phase A: a lane there needs the SAME 32-bit half (its wave's key fragment) and the same
-            // key group g of the four queries lg*4 + 0..3 -- stored as [qf][lg][g][half][r] they are one 16-byte read instead
-            // of four address computations and four 4-byte reads
-            const int i = t, ql = i >> 2, g = i & 3;
-            const uint64_t kw = (a.p > 0.f && q0 + ql < S) ? c_bits[0] : ~(uint64_t)0;
+            if (st < CQ) ldsLse[st] = q0 + st < S ? __builtin_bit_cast(float, o0[0]) * 1.44269504088896340736f : INFINITY;
+            // keep words, re-laid for phase A: a lane there needs the SAME 32-bit half (given by its key fragment) and the same
+            // key group g of the four queries lg*4 + 0..3 -- stored as [qf][lg][g][half][r] they are one 16-byte read
+            const int ql = st >> 2, g = st & 3;
+            const uint64_t kw = (a.p > 0.f && q0 + ql < S) ? ((uint64_t)o0[3] << 32 | o0[2]) : ~(uint64_t)0;
             uint32_t* bw = (uint32_t*)ldsBits + (((ql >> 2) * 4 + g) * 8 + (ql & 3));
             bw[0] = (uint32_t)kw; bw[4] = (uint32_t)(kw >> 32);
         }
     };
     load_chunk(0);
-    const float mk = kok ? mk_raw : -INFINITY;
-    const float mk2 = mk * 1.44269504088896340736f, sc2 = a.scale * 1.44269504088896340736f;
-    {   // K^T image and a zeroed dS tile
-        const u32x4 x0 = zsel(kr < S, kx0), x1 = zsel(kr + 1 < S, kx1);
-        const int pitch = KTP;
+    float mk2[RKPW];
 #pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const uint32_t lo = x0[w], hi = x1[w];
-            *(uint32_t*)(ldsKT + (kdc * 8 + 2 * w) * pitch + kr * 2) = (lo & 0xFFFFu) | (hi << 16);
-            *(uint32_t*)(ldsKT + (kdc * 8 + 2 * w + 1) * pitch + kr * 2) = (lo >> 16) | (hi & 0xFFFF0000u);
+    for (int j = 0; j < RKPW; ++j) mk2[j] = ((wave + RWV * j) * 16 + li < S ? mk_raw[j] : -INFINITY) * 1.44269504088896340736f;
+    const float sc2 = a.scale * 1.44269504088896340736f;
+    {   // K^T image and a zeroed dS tile
+#pragma unroll
+        for (int i = 0; i < KTI; ++i) {
+            const int it = t + i * RNT, kdc = it & 7, kr = (it >> 3) * 2;
+            const u32x4 x0 = zsel(kr < S, kx0[i]), x1 = zsel(kr + 1 < S, kx1[i]);
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const uint32_t lo = x0[w], hi = x1[w];
+                *(uint32_t*)(ldsKT + (kdc * 8 + 2 * w) * KTP + kr * 2) = (lo & 0xFFFFu) | (hi << 16);
+                *(uint32_t*)(ldsKT + (kdc * 8 + 2 * w + 1) * KTP + kr * 2) = (lo >> 16) | (hi & 0xFFFF0000u);
+            }
         }
-        for (int i = t; i < CQ * TSP / 8; i += FNT) *(uint64_t*)(ldsDS + i * 8) = 0;
+        for (int i = t; i < CQ * TSP / 8; i += RNT) *(uint64_t*)(ldsDS + i * 8) = 0;
     }
     use_set(0);
     store_chunk(0);
@@ -1243,67 +1255,67 @@ VB_KERNEL VB_LAUNCH_BOUNDS(FNT) attn_bwd_fused_kernel(AttnArgs a) {
     if (CQ < S) load_chunk(CQ);
 
     // q/k/v bias gradients = column sums of dqkv over tokens.  This kernel holds dK^T, dV^T (and, block by block, dQ^T) in
-    // fp32 registers with the token index along the LANES (li): a 16-lane butterfly per value, once per workgroup, gives the
-    // per-sample sums, which leave through a [B][3H] workspace (one slot per workgroup: no same-address global atomics --
-    // those cost +140 us per layer in round 1) and a tiny reduction kernel.  Replaces an 85 us pass over dqkv per layer.
-    f32x4 dqsum = f32x4{0.f, 0.f, 0.f, 0.f};               // this wave's phase-B blocks all have df = wave & 3 (12 % 4 == 0)
+    // fp32 registers with the token index along the LANES (li): the per-sample sums leave through a [B][3H] workspace (one slot
+    // per workgroup: no same-address global atomics -- those cost +140 us per layer in round 1) and a tiny reduction kernel.
+    f32x4 dqsum = f32x4{0.f, 0.f, 0.f, 0.f};               // this wave's phase-B blocks all have df = wave
     int cur = 0;
     for (int q0 = 0; q0 < S; q0 += CQ, cur ^= 1) {
         use_set(cur);
+        const bool h1 = q0 + 16 < S;                       // wave-uniform: the chunk's second query fragment holds a real query
         // ---- phase A
-        if (wave_on) {
 #pragma unroll
-            for (int qc = 0; qc < CQ / 32; ++qc) {
-                if (q0 + qc * 32 >= S) continue;
-                f32x4 pd[2], dsv[2];
+        for (int j = 0; j < RKPW; ++j) {
+            const int kf = wave + RWV * j;
+            // one fragment at a time: interleaved by the scheduler, the three fragments' S / P / dP / dS values are live together
+            // and spill
+            vb_sched_fence();
+            if (kf * 16 >= S) continue;                    // wave-uniform: no real key in this fragment (its dS columns stay 0)
+            f32x4 pd[2], dsv[2];
 #pragma unroll
-                for (int hf = 0; hf < 2; ++hf) {
-                    const int qf = 2 * qc + hf;            // fragment index inside the chunk
-                    if (hf == 1 && q0 + qf * 16 >= S) {    // wave-uniform: the second half of the LAST 32-query block is all padding
-                        pd[1] = f32x4{0.f, 0.f, 0.f, 0.f}; dsv[1] = pd[1];      // (S = 164: one fragment in twelve); phase B skips its rows too
-                        continue;
-                    }
-                    f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f}, dp = s;
-#pragma unroll
-                    for (int ks = 0; ks < 2; ++ks) {
-                        s = vb_mma(frag_rm(ldsQ, qf * 16 + li, ks, lg, T()), kb[ks], s);
-                        dp = vb_mma(frag_rm(ldsDO, qf * 16 + li, ks, lg, T()), vb[ks], dp);
-                    }
-                    // lane: key = kf*16 + li (column), queries q0 + qf*16 + lg*4 + r (rows)
-                    const f32x4 lse4 = *(const f32x4*)(ldsLse + qf * 16 + lg * 4);         // already times log2(e)
-                    const f32x4 d4 = *(const f32x4*)(ldsD + qf * 16 + lg * 4);
-                    // this wave's nibble of the keep words lies in ONE 32-bit half (kf is wave-uniform); the four queries'
-                    // halves are adjacent (see store_chunk); one select per probability yields the factor for both products
-                    const u32x4 w4 = *(const u32x4*)((const uint32_t*)ldsBits + (((qf * 4 + lg) * 4 + (li >> 2)) * 2 + ((kf & 15) >> 3)) * 4);
-                    // p = exp(s * scale + mask - lse) = exp2(s * (scale log2 e) + (mask log2 e - lse log2 e)): two packed
-                    // instructions per two probabilities instead of an fma, a subtract and a multiply each
-                    f32x4 xe;
-#pragma unroll
-                    for (int r = 0; r < 4; r += 2) {
-                        const f32x2 c = vb_splat2(mk2) - f32x2{lse4[r], lse4[r + 1]};
-                        const f32x2 x = vb_fma2(f32x2{s[r], s[r + 1]}, vb_splat2(sc2), c);
-                        xe[r] = x[0]; xe[r + 1] = x[1];
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int ql = qf * 16 + lg * 4 + r;
-                        const float p = fast_exp2(xe[r]);
-                        const float kscale = ((w4[r] >> ((kf & 7) * 4 + (li & 3))) & 1u) ? a.inv_keep : 0.f;
-                        const float pdrop = p * kscale;
-                        const float dpv = dp[r] * kscale;
-                        pd[hf][r] = pdrop;
-                        dsv[hf][r] = p * (dpv - d4[r]);             // dS / scale: the factor goes onto dK^T and dQ^T once (below)
-                        *(bf16*)(ldsDS + ql * TSP + (kf * 16 + li) * 2) = (bf16)dsv[hf][r];      // dS / scale as [query][key]
-                    }
+            for (int hf = 0; hf < 2; ++hf) {
+                if (hf == 1 && !h1) {                      // wave-uniform: the second half of the LAST chunk is all padding
+                    pd[1] = f32x4{0.f, 0.f, 0.f, 0.f}; dsv[1] = pd[1];      // phase B skips its rows too
+                    continue;
                 }
-                bf16x8 pb, dsb;
-                pack_b(pb, pd[0], pd[1]);
-                pack_b(dsb, dsv[0], dsv[1]);
+                f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f}, dp = s;
 #pragma unroll
-                for (int df = 0; df < 4; ++df) {
-                    dvT[df] = vb_mma(frag_tr(ldsDOT, tr_pitch<T>(CQ), df * 16 + li, qc, lg, T()), pb, dvT[df]);
-                    dkT[df] = vb_mma(frag_tr(ldsQT, tr_pitch<T>(CQ), df * 16 + li, qc, lg, T()), dsb, dkT[df]);
+                for (int ks = 0; ks < 2; ++ks) {
+                    s = vb_mma(frag_rm(ldsQ, hf * 16 + li, ks, lg, T()), kb[j][ks], s);
+                    dp = vb_mma(frag_rm(ldsDO, hf * 16 + li, ks, lg, T()), vb[j][ks], dp);
                 }
+                // lane: key = kf*16 + li (column), queries q0 + hf*16 + lg*4 + r (rows)
+                const f32x4 lse4 = *(const f32x4*)(ldsLse + hf * 16 + lg * 4);         // already times log2(e)
+                const f32x4 d4 = *(const f32x4*)(ldsD + hf * 16 + lg * 4);
+                // this fragment's nibble of the keep words lies in ONE 32-bit half; the four queries' halves are adjacent
+                // (see store_chunk); one select per probability yields the factor for both products
+                const u32x4 w4 = *(const u32x4*)((const uint32_t*)ldsBits + (((hf * 4 + lg) * 4 + (li >> 2)) * 2 + ((kf & 15) >> 3)) * 4);
+                // p = exp(s * scale + mask - lse) = exp2(s * (scale log2 e) + (mask log2 e - lse log2 e))
+                f32x4 xe;
+#pragma unroll
+                for (int r = 0; r < 4; r += 2) {
+                    const f32x2 c = vb_splat2(mk2[j]) - f32x2{lse4[r], lse4[r + 1]};
+                    const f32x2 x = vb_fma2(f32x2{s[r], s[r + 1]}, vb_splat2(sc2), c);
+                    xe[r] = x[0]; xe[r + 1] = x[1];
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int ql = hf * 16 + lg * 4 + r;
+                    const float p = fast_exp2(xe[r]);
+                    const float kscale = ((w4[r] >> ((kf & 7) * 4 + (li & 3))) & 1u) ? a.inv_keep : 0.f;
+                    const float pdrop = p * kscale;
+                    const float dpv = dp[r] * kscale;
+                    pd[hf][r] = pdrop;
+                    dsv[hf][r] = p * (dpv - d4[r]);             // dS / scale: the factor goes onto dK^T and dQ^T once (below)
+                    *(bf16*)(ldsDS + ql * TSP + (kf * 16 + li) * 2) = (bf16)dsv[hf][r];      // dS / scale as [query][key]
+                }
+            }
+            bf16x8 pb, dsb;
+            pack_b(pb, pd[0], pd[1]);
+            pack_b(dsb, dsv[0], dsv[1]);
+#pragma unroll
+            for (int df = 0; df < 4; ++df) {
+                dvT[j][df] = vb_mma(frag_tr(ldsDOT, tr_pitch<T>(CQ), df * 16 + li, 0, lg, T()), pb, dvT[j][df]);
+                dkT[j][df] = vb_mma(frag_tr(ldsQT, tr_pitch<T>(CQ), df * 16 + li, 0, lg, T()), dsb, dkT[j][df]);
             }
         }
         if (q0 + CQ < S) {                                 // the next chunk's images go to the other set meanwhile
@@ -1312,100 +1324,94 @@ VB_KERNEL VB_LAUNCH_BOUNDS(FNT) attn_bwd_fused_kernel(AttnArgs a) {
         }
         __syncthreads();                                   // the chunk's dS tile is complete, the next chunk is staged
         if (q0 + 2 * CQ < S) load_chunk(q0 + 2 * CQ);
-        // ---- phase B: dQ^T block (d rows df*16.., query columns qf*16..) = K^T dS^T over all keys.  16 blocks, 12 waves:
-        // wave w owns block w (qf = w >> 2, df = w & 3) and waves 0..3 also block w + 12 (qf = 3, the SAME df): the two are
-        // computed together -- one K^T fragment feeds both, and their MFMA chains (six dependent instructions each) overlap
-        // instead of running back to back on the four waves the whole workgroup then waits for
+        // ---- phase B: dQ^T block (d rows df*16.., query columns qf*16..) = K^T dS^T over all keys.  8 blocks, 4 waves: wave w
+        // owns d block w of both query fragments -- one K^T fragment feeds both MFMA chains, which overlap
         {
-            static_assert(CQ == 64 && FWPB == 12, "block ownership below assumes 16 blocks on 12 waves");
-            const int df = wave & 3, qf0 = wave >> 2, qf1 = 3;
-            const bool v0 = q0 + qf0 * 16 < S, v1 = wave < 4 && q0 + qf1 * 16 < S;      // wave-uniform
-            if (v0 || v1) {
-                f32x4 acc0 = f32x4{0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
+            const int df = wave;
+            f32x4 acc0 = f32x4{0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
 #pragma unroll
-                for (int ks = 0; ks < FNK / 32; ++ks) {
-                    if (ks * 32 >= S) continue;
-                    // B operand: lane (n = query li, g = lg) holds dS[q][key(g, j)], key(g, j) = 32 ks + 16 (j >> 2) + 4 g + (j & 3)
-                    const bf16x8 kt = frag_tr(ldsKT, KTP, df * 16 + li, ks, lg, T());
-                    if (v0) {
-                        const unsigned char* src = ldsDS + (qf0 * 16 + li) * TSP + (32 * ks + 4 * lg) * 2;
-                        const bf16x4 lo = *(const bf16x4*)src, hi = *(const bf16x4*)(src + 32);
-                        acc0 = vb_mma(kt, bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}, acc0);
-                    }
-                    if (v1) {
-                        const unsigned char* src = ldsDS + (qf1 * 16 + li) * TSP + (32 * ks + 4 * lg) * 2;
-                        const bf16x4 lo = *(const bf16x4*)src, hi = *(const bf16x4*)(src + 32);
-                        acc1 = vb_mma(kt, bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}, acc1);
-                    }
+            for (int ks = 0; ks < FNK / 32; ++ks) {
+                if (ks * 32 >= S) continue;
+                // B operand: lane (n = query li, g = lg) holds dS[q][key(g, j)], key(g, j) = 32 ks + 16 (j >> 2) + 4 g + (j & 3)
+                const bf16x8 kt = frag_tr(ldsKT, KTP, df * 16 + li, ks, lg, T());
+                {
+                    const unsigned char* src = ldsDS + li * TSP + (32 * ks + 4 * lg) * 2;
+                    const bf16x4 lo = *(const bf16x4*)src, hi = *(const bf16x4*)(src + 32);
+                    acc0 = vb_mma(kt, bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}, acc0);
                 }
-                // dQ rows: 32-bit byte offsets from the scalar base (the launcher checks tokens x pitch x 2 < 2^32) -- a 64-bit lane
-                // address here is a register pair the kernel (at its 168-register budget) spills, and its scratch reload's
-                // vmcnt(0) also waits for the chunk fetch in flight
-                const unsigned dq_col = (unsigned)(h * D + df * 16 + lg * 4) * 2u;
-                unsigned char* const dq_base = (unsigned char*)a.dqkv;
-                if (v0) {
-                    const int q = q0 + qf0 * 16 + li;
-                    acc0 *= a.scale;                        // the score scale left out of dS in phase A
-                    if (q < S) store4((T*)(dq_base + ((unsigned)((int)row0 + q) * (unsigned)((int)ldx * 2) + dq_col)), acc0);
-                    dqsum += acc0;                          // columns of padded queries are exactly 0 (their dS rows are)
+                if (h1) {
+                    const unsigned char* src = ldsDS + (16 + li) * TSP + (32 * ks + 4 * lg) * 2;
+                    const bf16x4 lo = *(const bf16x4*)src, hi = *(const bf16x4*)(src + 32);
+                    acc1 = vb_mma(kt, bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}, acc1);
                 }
-                if (v1) {
-                    const int q = q0 + qf1 * 16 + li;
-                    acc1 *= a.scale;
-                    if (q < S) store4((T*)(dq_base + ((unsigned)((int)row0 + q) * (unsigned)((int)ldx * 2) + dq_col)), acc1);
-                    dqsum += acc1;
-                }
+            }
+            // dQ rows: 32-bit byte offsets from the scalar base (the launcher checks tokens x pitch x 2 < 2^32)
+            const unsigned dq_col = (unsigned)(h * D + df * 16 + lg * 4) * 2u;
+            unsigned char* const dq_base = (unsigned char*)a.dqkv;
+            {
+                const int q = q0 + li;
+                acc0 *= a.scale;                            // the score scale left out of dS in phase A
+                if (q < S) store4((T*)(dq_base + ((unsigned)((int)row0 + q) * (unsigned)((int)ldx * 2) + dq_col)), acc0);
+                dqsum += acc0;                              // columns of padded queries are exactly 0 (their dS rows are)
+            }
+            if (h1) {
+                const int q = q0 + 16 + li;
+                acc1 *= a.scale;
+                if (q < S) store4((T*)(dq_base + ((unsigned)((int)row0 + q) * (unsigned)((int)ldx * 2) + dq_col)), acc1);
+                dqsum += acc1;
             }
         }
         __syncthreads();                                   // phase B is done with the tile before the next phase A writes it
     }
-#pragma unroll
-    for (int df = 0; df < 4; ++df) dkT[df] *= a.scale;     // dK^T was accumulated from dS / scale (phase A): one multiply per output
     {   // 16-byte stores (store4x2: every lane takes part in the lane exchange, the store is predicated on a real key)
-        T* dkrow = (T*)a.dqkv + (row0 + keyc) * ldx + H + h * D;
-        T* dvrow = (T*)a.dqkv + (row0 + keyc) * ldx + 2 * H + h * D;
         const bool wide = wide_ok(a.dqkv, ldx);
 #pragma unroll
-        for (int dj = 0; dj < 2; ++dj) {
-            store4x2(dkrow + dj * 32, lg, dkT[2 * dj], dkT[2 * dj + 1], kok, wide);
-            store4x2(dvrow + dj * 32, lg, dvT[2 * dj], dvT[2 * dj + 1], kok, wide);
+        for (int j = 0; j < RKPW; ++j) {
+            const int key = (wave + RWV * j) * 16 + li;
+            if ((wave + RWV * j) * 16 >= S) continue;      // wave-uniform
+#pragma unroll
+            for (int df = 0; df < 4; ++df) dkT[j][df] *= a.scale;    // dK^T was accumulated from dS / scale: one multiply per output
+            const bool kok = key < S;
+            const int keyc = kok ? key : S - 1;
+            T* dkrow = (T*)a.dqkv + (row0 + keyc) * ldx + H + h * D;
+            T* dvrow = (T*)a.dqkv + (row0 + keyc) * ldx + 2 * H + h * D;
+#pragma unroll
+            for (int dj = 0; dj < 2; ++dj) {
+                store4x2(dkrow + dj * 32, lg, dkT[j][2 * dj], dkT[j][2 * dj + 1], kok, wide);
+                store4x2(dvrow + dj * 32, lg, dvT[j][2 * dj], dvT[j][2 * dj + 1], kok, wide);
+            }
         }
     }
     if (a.bias_ws) {
-        // every LDS image is idle now (the loop ended on a barrier): each lane parks its 36 accumulators (4 dQ sums, 16 dK^T,
-        // 16 dV^T) as raw[wave][value][lane] -- 36 conflict-free ds_write_b32 -- and 192 threads add up, per output column d,
-        // the 16 lanes (keys / queries) x the waves that hold it.  (The first form reduced inside each wave with 36 DPP
-        // row sums per lane before going to LDS: ~5000 of the workgroup's ~45000 cycles, by the in-kernel cycle trace.)
-        float* raw = (float*)smem;                          // 12 x 36 x 64 floats = 108 KB of the 124 KB
+        // every LDS image is idle now (the loop ended on a barrier): each lane adds its fragments' accumulators (padded keys and
+        // fragments without a real key hold exact zeros), parks the 36 sums (4 dQ, 16 dK^T, 16 dV^T) as raw[wave][value][lane]
+        // -- conflict-free ds_write_b32 -- and 192 threads add up, per output column d, the 16 lanes x the waves that hold it
+        float* raw = (float*)smem;                          // 4 x 36 x 64 floats = 36 KB
         constexpr int NV = 4 + 2 * 16;
-        static_assert((size_t)FWPB * NV * 64 * 4 <= 2 * (size_t)SETB + KT_BYTES + (size_t)CQ * TSP, "raw partials fit the idle images");
+        static_assert((size_t)RWV * NV * 64 * 4 <= 2 * (size_t)SETB + KT_BYTES + (size_t)CQ * TSP, "raw partials fit the idle images");
         float* mine = raw + ((long)wave * NV) * 64 + lane;
 #pragma unroll
         for (int r = 0; r < 4; ++r) mine[r * 64] = dqsum[r];
 #pragma unroll
-        for (int df = 0; df < 4; ++df)
+        for (int df = 0; df < 4; ++df) {
+            const f32x4 ksum = (dkT[0][df] + dkT[1][df]) + dkT[2][df], vsum = (dvT[0][df] + dvT[1][df]) + dvT[2][df];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {                   // padded keys contribute exact zeros
-                mine[(4 + df * 4 + r) * 64] = dkT[df][r];
-                mine[(20 + df * 4 + r) * 64] = dvT[df][r];
+            for (int r = 0; r < 4; ++r) {
+                mine[(4 + df * 4 + r) * 64] = ksum[r];
+                mine[(20 + df * 4 + r) * 64] = vsum[r];
             }
+        }
         __syncthreads();
         if (t < 3 * D) {
             const int which = t / D, dd = t % D, df = dd >> 4, glg = (dd >> 2) & 3, r = dd & 3;
             float sum = 0.f;
-            if (which == 0) {                               // dQ^T block df lives in the waves with (wave & 3) == df
-                for (int w = df; w < FWPB; w += 4) {
-                    const f32x4* src = (const f32x4*)(raw + ((long)w * NV + r) * 64 + glg * 16);
+            // dQ^T block df lives in wave df only; dK^T / dV^T column d in every wave
+            const int w0 = which == 0 ? df : 0, w1 = which == 0 ? df + 1 : RWV;
+            const int v = which == 0 ? r : (which == 1 ? 4 : 20) + df * 4 + r;
+            for (int w = w0; w < w1; ++w) {
+                const f32x4* src = (const f32x4*)(raw + ((long)w * NV + v) * 64 + glg * 16);
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) { const f32x4 x = src[i]; sum += (x[0] + x[1]) + (x[2] + x[3]); }
-                }
-            } else {
-                const int v = (which == 1 ? 4 : 20) + df * 4 + r;
-                for (int w = 0; w < FWPB; ++w) {
-                    const f32x4* src = (const f32x4*)(raw + ((long)w * NV + v) * 64 + glg * 16);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) { const f32x4 x = src[i]; sum += (x[0] + x[1]) + (x[2] + x[3]); }
-                }
+                for (int i = 0; i < 4; ++i) { const f32x4 x = src[i]; sum += (x[0] + x[1]) + (x[2] + x[3]); }
             }
             a.bias_ws[((long)b * 3 + which) * H + h * D + dd] = sum;
         }
@@ -1427,10 +1433,8 @@ VB_KERNEL VB_LAUNCH_BOUNDS(256) attn_bias_reduce_kernel(const float* ws, float* 
     for (; bi < b1; ++bi) s0 += ws[(long)bi * C + c];
     vb_atomic_add_noret(out + c, (s0 + s1) + (s2 + s3));
 }
-template <int NKF, int CQ> size_t fused_smem() {
-    return 2 * (2 * rm_bytes<bf16>(CQ) + 2 * tr_bytes<bf16>(CQ) + 2 * CQ * 4 + (size_t)CQ * 4 * ((NKF + 15) / 16) * 8) +
-           KT_BYTES + (size_t)CQ * TSP;
-}
+template <int NKF> constexpr size_t resident_smem() { return 2 * (size_t)resident_setb<NKF>() + KT_BYTES + (size_t)RCQ * TSP; }
+static_assert(2 * resident_smem<12>() <= 160 * 1024, "two workgroups of the one-pass backward per CU");
 
 template <typename T, int NKF> size_t fwd_smem() { return rm_bytes<T>(NKF * 16) + tr_bytes<T>((NKF + 1) / 2 * 32) + NKF * 16 * 4; }
 template <typename T, int NKF> size_t dq_smem() { return 2 * rm_bytes<T>(NKF * 16) + tr_bytes<T>(NKF * 16) + NKF * 16 * 4; }
@@ -1466,14 +1470,12 @@ int launch_all(int which, const AttnArgs& a, hipStream_t s) {
             VB_LAUNCH((attn_fwd_kernel<T, NKF>), grid, block, sm, s, a);
         }
     } else {
-        // (S <= 64: only 4 of the one-pass kernel's 12 waves own a key fragment -- the two-pass form plus the separate
-        //  bias-gradient pass is faster there: 349 + ~85 us against 483 us per layer at 86 k tokens, S = 56)
+        // (S <= 64: the two-pass form plus the separate bias-gradient pass was faster there than the 12-wave one-pass form this
+        //  kernel replaced -- 349 + ~85 us against 483 us per layer at 86 k tokens, S = 56 -- and is kept: not re-measured)
         if constexpr (sizeof(T) == 2 && NKF <= 12 && NKF > 4) {
-            if (a.ctx_fwd && a.qkv && a.Sq == a.S && a.S <= FWPB * 16 && vb_opts_for((void*)s).attn_two_pass != 1 &&
+            if (a.ctx_fwd && a.qkv && a.Sq == a.S && a.S <= FNK && vb_opts_for((void*)s).attn_two_pass != 1 &&
                 (long)a.B * a.S * 3 * a.nh * D * 2 < (1L << 32)) {   // one-pass backward (needs the forward output; 32-bit byte offsets)
-                // 64-query chunks (86 KB of LDS, one workgroup per CU): 528-541 us per layer at B=512; 32-query chunks (two
-                // workgroups per CU, twice the barriers): 575 us
-                VB_LAUNCH((attn_bwd_fused_kernel<NKF, 64>), grid, dim3(FNT), (fused_smem<NKF, 64>()), s, a);
+                VB_LAUNCH((attn_bwd_resident_kernel<NKF>), grid, dim3(RNT), resident_smem<NKF>(), s, a);
                 return vb_check_launch() == VB_OK ? 1 : VB_ERR_LAUNCH;      // 1: the bias workspace (if any) was filled
             }
         }
