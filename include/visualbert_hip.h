@@ -280,6 +280,32 @@ int vb_bert_adam_step(float* params, const float* grads, float* exp_avg, float* 
                       const int64_t* tensor_table, int n_tensors, const float* touched, float* norm2_ws, int* step_counters,
                       float lr, float b1, float b2, float eps, float weight_decay,
                       float max_grad_norm, float warmup, float t_total, int schedule, void* stream);
+/* ------------------------------------------------------------------------------------------------
+ * The same step with PER-GROUP hyper-parameters: the reference's BertAdam reads lr, schedule, b1, b2, e, weight_decay and
+ * max_grad_norm from each parameter group (optimization.py:262-301).  Arena, chunk_table, tensor_table, touched, norm2_ws and
+ * step_counters are those of vb_bert_adam_step; the scalars are replaced by a device-resident table
+ * group_table: fp64[n_groups][11] = {lr, b1, b2, eps, weight_decay, max_grad_norm, schedule code, warmup, t_total, cycles,
+ * host multiplier}, and tensor t belongs to group (tensor_table[t].flags >> 2) -- the bits above bit0 / bit1, so the entry keeps
+ * its int64 x 4 form and vb_refresh_bf16_shadow reads the same table.  bit1 is NOT read here: the group's weight_decay applies
+ * (0: none).  max_grad_norm <= 0: no clipping for that group; the norms are computed for the tensors of groups that clip, for all
+ * when touched is given.
+ * schedule code (the classes of optimization.py:83-173), evaluated in double from the tensor's own step counter read before its
+ * increment; t_total < 0 gives 1 for every class:
+ *   0 ConstantLR   1 WarmupLinearSchedule   2 WarmupConstantSchedule   3 WarmupCosineSchedule
+ *   4 WarmupCosineWithHardRestartsSchedule   5 WarmupCosineWithWarmupRestartsSchedule (warmup already multiplied by cycles, as
+ *   the class keeps it)   6 the host supplies this step's multiplier in the row's last column (user subclasses of _LRSchedule)
+ * The per-element arithmetic, the skip rule and the counter increment are those of vb_bert_adam_step: a table of equal rows
+ * gives bit-identical results to it.
+ * validate != 0: both tables are read back first (this waits for the stream; not inside a graph capture) and VB_ERR_ARG is
+ * returned, with nothing changed, for a group id >= n_groups on an optimised tensor or an unknown schedule code.
+ * validate == 0 (the steady state: no host<->device traffic): such a tensor takes no step; nothing outside the table is read.
+ * A NULL table or n_groups <= 0 is VB_ERR_ARG either way.
+ * Replaces BertAdam.step, optimization.py:239-304 (+ the schedules, :55-173).
+ * ---------------------------------------------------------------------------------------------- */
+int vb_bert_adam_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                             void* bf16_shadow, const int64_t* chunk_table, int n_chunks,
+                             const int64_t* tensor_table, int n_tensors, const float* touched, float* norm2_ws, int* step_counters,
+                             const double* group_table, int n_groups, int validate, void* stream);
 int vb_refresh_bf16_shadow(const float* params, void* bf16_shadow, const int64_t* chunk_table,
                            int n_chunks, const int64_t* tensor_table, void* stream);
 /* W^T copies of the bf16 GEMM weights (so dgrad dx = dy W is a K-contiguous x K-contiguous GEMM):

@@ -12,6 +12,8 @@
 // HBM traffic per parameter: read p, g, m, v (16 B) + write p, m, v (12 B) [+ 2 B shadow] = 28-30 B.
 // Everything the step needs lives on the device (chunk table, step counters, hyper-parameters): no
 // host<->device traffic per step, so the step can sit in a captured graph.
+// Two entries share the element loop: vb_bert_adam_step (one set of scalar hyper-parameters) and
+// vb_bert_adam_step_groups (a device-resident table with one row per parameter group, :262-301).
 #include "vb_rt.h"
 #include "../../include/visualbert_hip.h"
 
@@ -30,10 +32,7 @@ struct AdamHyper {
 // Squared gradient norms per tensor, DETERMINISTICALLY: a chunk's partial goes to its own slot and one thread per tensor
 // adds its chunks' partials in table order.  (A float atomic per chunk made the clip coefficient differ in the last bit
 // from run to run -- and between data-parallel replicas, whose weights then drift apart ulp by ulp.)
-VB_KERNEL VB_LAUNCH_BOUNDS(NT) adam_norm_kernel(const float* grads, const int64_t* chunks, float* partial) {
-    VB_DYN_SMEM(smem);
-    float* red = (float*)smem;
-    const int64_t* c = chunks + (long)blockIdx.x * 4;
+VB_DEVICE void chunk_norm2(const float* grads, const int64_t* c, float* red, float* out) {
     const long off = c[1], len = c[2];
     float s = 0.f;
     if (((off | len) & 3) == 0) {
@@ -54,7 +53,11 @@ VB_KERNEL VB_LAUNCH_BOUNDS(NT) adam_norm_kernel(const float* grads, const int64_
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (threadIdx.x == 0) *out = (red[0] + red[1]) + (red[2] + red[3]);
+}
+VB_KERNEL VB_LAUNCH_BOUNDS(NT) adam_norm_kernel(const float* grads, const int64_t* chunks, float* partial) {
+    VB_DYN_SMEM(smem);
+    chunk_norm2(grads, chunks + (long)blockIdx.x * 4, (float*)smem, partial + blockIdx.x);
 }
 // one wave per tensor (the workgroup of the tensor's FIRST chunk; the others leave): lane l adds the partials of chunks
 // l, l + 64, ... in that order, then a fixed butterfly -- the same bits every time
@@ -95,6 +98,25 @@ VB_DEVICE bool adam_skips(const float* touched, const float* norm2, const int* s
     return !(norm2[tid] > 0.f);
 }
 
+// one chunk of one tensor, every hyper-parameter already reduced to the six floats of this tensor and step
+// (4-byte accesses on purpose: a wave's load is 256 contiguous bytes per array and many of them are in flight.  The 16-byte form --
+// a quarter of the memory instructions -- measured SLOWER in the step, 632 vs 554 us at B = 8 on the 3.3 GB pass; round 6, not kept)
+VB_DEVICE void adam_update_chunk(float* params, const float* grads, float* m, float* v, bf16* shadow, long off, long len,
+                                 long t_off, long sh_off, float lr, float b1, float b2, float eps, float wd, float clip) {
+    for (long i = threadIdx.x; i < len; i += NT) {
+        const long e = off + i;
+        const float g = grads[e] * clip;
+        const float p = params[e];
+        const float mm = m[e] * b1 + (1.0f - b1) * g;
+        const float vv = v[e] * b2 + (1.0f - b2) * g * g;
+        float u = mm / (sqrtf(vv) + eps);
+        if (wd > 0.f) u += wd * p;
+        const float pn = p - lr * u;
+        m[e] = mm; v[e] = vv; params[e] = pn;
+        if (shadow && sh_off >= 0) shadow[sh_off + (e - t_off)] = (bf16)pn;
+    }
+}
+
 VB_KERNEL VB_LAUNCH_BOUNDS(NT) adam_update_kernel(float* params, const float* grads, float* m, float* v, bf16* shadow,
                                                  const int64_t* chunks, const int64_t* tensors, const float* norm2,
                                                  const int* steps, const float* touched, AdamHyper h) {
@@ -111,25 +133,128 @@ VB_KERNEL VB_LAUNCH_BOUNDS(NT) adam_update_kernel(float* params, const float* gr
         clip = cc < 1.0f ? cc : 1.0f;
     }
     const float lr = h.lr * schedule_mult(h, steps[tid]);
-    // (4-byte accesses on purpose: a wave's load is 256 contiguous bytes per array and many of them are in flight.  The 16-byte form --
-    // a quarter of the memory instructions -- measured SLOWER in the step, 632 vs 554 us at B = 8 on the 3.3 GB pass; round 6, not kept)
-    for (long i = threadIdx.x; i < len; i += NT) {
-        const long e = off + i;
-        const float g = grads[e] * clip;
-        const float p = params[e];
-        const float mm = m[e] * h.b1 + (1.0f - h.b1) * g;
-        const float vv = v[e] * h.b2 + (1.0f - h.b2) * g * g;
-        float u = mm / (sqrtf(vv) + h.eps);
-        if (wd > 0.f) u += wd * p;
-        const float pn = p - lr * u;
-        m[e] = mm; v[e] = vv; params[e] = pn;
-        if (shadow && sh_off >= 0) shadow[sh_off + (e - t_off)] = (bf16)pn;
-    }
+    adam_update_chunk(params, grads, m, v, shadow, off, len, t_off, sh_off, lr, h.b1, h.b2, h.eps, wd, clip);
 }
 
 VB_KERNEL adam_step_inc_kernel(int* steps, const int64_t* tensors, int n, const float* touched, const float* norm2) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && (tensors[(long)i * 4 + 3] & 1) && !adam_skips(touched, norm2, steps, i)) steps[i] += 1;
+}
+
+// ---- per-group hyper-parameters (vb_bert_adam_step_groups) -------------------------------------------------------------
+// group table row (fp64 x GROUP_COLS): lr, b1, b2, eps, weight_decay, max_grad_norm, schedule code, warmup, t_total, cycles,
+// host multiplier.  A tensor's group id is flags >> 2 of its tensor-table entry.  A chunk belongs to one tensor, so its row is
+// uniform per workgroup: it is read (scalar loads) and reduced to six floats before the element loop, which is the loop of
+// adam_update_kernel.
+constexpr int GROUP_COLS = 11;
+enum { G_LR = 0, G_B1, G_B2, G_EPS, G_WD, G_CLIP, G_SCHED, G_WARMUP, G_TTOTAL, G_CYCLES, G_HOSTMULT };
+enum { SCHED_NONE = 0, SCHED_WARMUP_LINEAR, SCHED_WARMUP_CONSTANT, SCHED_WARMUP_COSINE, SCHED_COSINE_HARD_RESTARTS,
+       SCHED_COSINE_WARMUP_RESTARTS, SCHED_HOST, SCHED_COUNT };
+
+// the row of tensor `tid`, or NULL when the tensor takes no part: not optimised, or -- only reachable when the caller passed
+// validate = 0 with a bad table -- a group id outside the table or an unknown schedule code (never read outside the table)
+VB_DEVICE const double* adam_group_row(const int64_t* tensors, long tid, const double* groups, int n_groups) {
+    const long flags = tensors[tid * 4 + 3];
+    if (!(flags & 1)) return nullptr;
+    const long gid = flags >> 2;
+    if (gid < 0 || gid >= n_groups) return nullptr;
+    const double* row = groups + gid * GROUP_COLS;
+    const double code = row[G_SCHED];
+    if (!(code >= 0.0 && code < (double)SCHED_COUNT) || code != (double)(int)code) return nullptr;
+    return row;
+}
+
+// _LRSchedule.get_lr and the get_lr_ of its six classes (optimization.py:55-73, :83-173), in double and in the reference's
+// operation order (no contraction: -ffp-contract=off).  progress is never negative, so Python's float % is fmod.
+VB_DEVICE double schedule_mult_group(const double* row, int step) {
+    const int code = (int)row[G_SCHED];
+    if (code == SCHED_HOST) return row[G_HOSTMULT];
+    const double t_total = row[G_TTOTAL];
+    if (code == SCHED_NONE || t_total < 0.0) return 1.0;
+    const double w = row[G_WARMUP] > 0.0 ? row[G_WARMUP] : 0.0, cycles = row[G_CYCLES];
+    const double pi = 3.141592653589793;
+    double progress = (double)step / t_total;
+    if (code == SCHED_COSINE_WARMUP_RESTARTS) progress = fmod(progress * cycles, 1.0);
+    if (progress < w) return progress / w;
+    if (code == SCHED_WARMUP_CONSTANT) return 1.0;
+    if (code == SCHED_WARMUP_LINEAR) { const double r = (progress - 1.0) / (w - 1.0); return r < 0.0 ? 0.0 : r; }
+    progress = (progress - w) / (1.0 - w);
+    if (code == SCHED_WARMUP_COSINE) return 0.5 * (1.0 + cos(pi * cycles * 2.0 * progress));
+    if (code == SCHED_COSINE_HARD_RESTARTS) return 0.5 * (1.0 + cos(pi * fmod(cycles * progress, 1.0)));
+    return 0.5 * (1.0 + cos(pi * progress));
+}
+
+// the norm of a chunk is needed when its tensor's group clips or when the skip rule will read it (touched given); otherwise its
+// slot is zeroed, so that the finish kernel still sums defined values
+VB_KERNEL VB_LAUNCH_BOUNDS(NT) adam_norm_groups_kernel(const float* grads, const int64_t* chunks, const int64_t* tensors,
+                                                      const double* groups, int n_groups, const float* touched, float* partial) {
+    VB_DYN_SMEM(smem);
+    const int64_t* c = chunks + (long)blockIdx.x * 4;
+    const double* row = adam_group_row(tensors, c[0], groups, n_groups);
+    if (!row || (!touched && !(row[G_CLIP] > 0.0))) {
+        if (threadIdx.x == 0) partial[blockIdx.x] = 0.f;
+        return;
+    }
+    chunk_norm2(grads, c, (float*)smem, partial + blockIdx.x);
+}
+
+VB_KERNEL VB_LAUNCH_BOUNDS(NT) adam_update_groups_kernel(float* params, const float* grads, float* m, float* v, bf16* shadow,
+                                                        const int64_t* chunks, const int64_t* tensors, const float* norm2,
+                                                        const int* steps, const float* touched, const double* groups,
+                                                        int n_groups) {
+    const int64_t* c = chunks + (long)blockIdx.x * 4;
+    const long tid = c[0], off = c[1], len = c[2];
+    const double* row = adam_group_row(tensors, tid, groups, n_groups);
+    if (!row) return;
+    if (adam_skips(touched, norm2, steps, tid)) return;
+    const int64_t* te = tensors + tid * 4;
+    const long t_off = te[0], sh_off = te[2];
+    const float max_grad_norm = (float)row[G_CLIP];
+    float clip = 1.0f;
+    if (max_grad_norm > 0.f) {
+        const float cc = max_grad_norm / (sqrtf(norm2[tid]) + 1e-6f);
+        clip = cc < 1.0f ? cc : 1.0f;
+    }
+    const float lr = (float)row[G_LR] * (float)schedule_mult_group(row, steps[tid]);
+    adam_update_chunk(params, grads, m, v, shadow, off, len, t_off, sh_off, lr, (float)row[G_B1], (float)row[G_B2],
+                      (float)row[G_EPS], (float)row[G_WD], clip);
+}
+
+VB_KERNEL adam_step_inc_groups_kernel(int* steps, const int64_t* tensors, int n, const float* touched, const float* norm2,
+                                      const double* groups, int n_groups) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && adam_group_row(tensors, i, groups, n_groups) && !adam_skips(touched, norm2, steps, i)) steps[i] += 1;
+}
+
+// argument check of the device-resident tables: they are read back (this waits for the stream), so the caller asks for it only
+// when a table is new
+static int adam_groups_validate(const int64_t* tensor_table, int n_tensors, const double* group_table, int n_groups,
+                                hipStream_t s) {
+    int64_t* tt = (int64_t*)malloc((size_t)n_tensors * 4 * sizeof(int64_t));
+    double* gt = (double*)malloc((size_t)n_groups * GROUP_COLS * sizeof(double));
+    int rc = (tt && gt) ? VB_OK : VB_ERR_LAUNCH;
+#ifdef VB_EMU
+    if (rc == VB_OK) {
+        memcpy(tt, tensor_table, (size_t)n_tensors * 4 * sizeof(int64_t));
+        memcpy(gt, group_table, (size_t)n_groups * GROUP_COLS * sizeof(double));
+    }
+#else
+    if (rc == VB_OK && (hipMemcpyAsync(tt, tensor_table, (size_t)n_tensors * 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+                        hipMemcpyAsync(gt, group_table, (size_t)n_groups * GROUP_COLS * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess ||
+                        hipStreamSynchronize(s) != hipSuccess))
+        rc = VB_ERR_LAUNCH;
+#endif
+    for (int i = 0; rc == VB_OK && i < n_tensors; ++i) {
+        const int64_t flags = tt[(size_t)i * 4 + 3];
+        if ((flags & 1) && ((flags >> 2) < 0 || (flags >> 2) >= n_groups)) rc = VB_ERR_ARG;
+    }
+    for (int g = 0; rc == VB_OK && g < n_groups; ++g) {
+        const double code = gt[(size_t)g * GROUP_COLS + G_SCHED];
+        if (!(code >= 0.0 && code < (double)SCHED_COUNT) || code != (double)(int)code) rc = VB_ERR_ARG;
+    }
+    free(tt);
+    free(gt);
+    return rc;
 }
 
 VB_KERNEL VB_LAUNCH_BOUNDS(NT) shadow_refresh_kernel(const float* params, bf16* shadow, const int64_t* chunks,
@@ -212,6 +337,34 @@ extern "C" int vb_bert_adam_step(float* params, const float* grads, float* exp_a
               (bf16*)bf16_shadow, chunk_table, tensor_table, (const float*)norm2_ws, (const int*)step_counters, touched, h);
     VB_LAUNCH(adam_step_inc_kernel, dim3((unsigned)((n_tensors + 63) / 64)), dim3(64), 0, s, step_counters,
               tensor_table, n_tensors, touched, (const float*)norm2_ws);
+    return vb_check_launch();
+}
+
+extern "C" int vb_bert_adam_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                        void* bf16_shadow, const int64_t* chunk_table, int n_chunks,
+                                        const int64_t* tensor_table, int n_tensors, const float* touched, float* norm2_ws,
+                                        int* step_counters, const double* group_table, int n_groups, int validate,
+                                        void* stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !chunk_table || !tensor_table || !norm2_ws || !step_counters)
+        return VB_ERR_ARG;
+    if (n_chunks <= 0 || n_tensors <= 0 || !group_table || n_groups <= 0) return VB_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    if (validate) {
+        const int rc = adam_groups_validate(tensor_table, n_tensors, group_table, n_groups, s);
+        if (rc != VB_OK) return rc;
+    }
+    // whether a group clips is in the table, on the device: the norm kernel decides per chunk (a chunk that needs no norm costs
+    // one empty workgroup)
+    float* partial = norm2_ws + n_tensors;                  // [n_chunks]
+    VB_LAUNCH(adam_norm_groups_kernel, dim3((unsigned)n_chunks), dim3(NT), 64, s, grads, chunk_table, tensor_table,
+              group_table, n_groups, touched, partial);
+    VB_LAUNCH(adam_norm_finish_kernel, dim3((unsigned)n_chunks), dim3(64), 0, s, chunk_table, n_chunks,
+              (const float*)partial, norm2_ws);
+    VB_LAUNCH(adam_update_groups_kernel, dim3((unsigned)n_chunks), dim3(NT), 0, s, params, grads, exp_avg, exp_avg_sq,
+              (bf16*)bf16_shadow, chunk_table, tensor_table, (const float*)norm2_ws, (const int*)step_counters, touched,
+              group_table, n_groups);
+    VB_LAUNCH(adam_step_inc_groups_kernel, dim3((unsigned)((n_tensors + 63) / 64)), dim3(64), 0, s, step_counters,
+              tensor_table, n_tensors, touched, (const float*)norm2_ws, group_table, n_groups);
     return vb_check_launch();
 }
 

@@ -15,7 +15,7 @@ from torch import nn
 
 from . import ops
 from .modeling import BertConfig, TrainVisualBERTObjective
-from .optimization import BertAdam
+from .optimization import BertAdam, layerwise_groups
 
 
 class VisualBERTFixedImageEmbedding(nn.Module):
@@ -245,9 +245,14 @@ class ModelWrapper(object):
         param_optimizer = [n for n in self.model.named_parameters() if "pooler" not in n[0]]
         self.optimizer_param_names = [n for n, _ in param_optimizer]
         no_decay = ["bias", "LayerNorm.bias", "LayerNorm.weight"]
-        groups = [
-            {"params": [p for n, p in param_optimizer if not any(nd in n for nd in no_decay)], "weight_decay": 0.01},
-            {"params": [p for n, p in param_optimizer if any(nd in n for nd in no_decay)], "weight_decay": 0.0}]
+        if "layerwise_lr_decay" in args or "head_learning_rate" in args:
+            # fine-tuning recipes (not in the reference's wrapper): a learning rate per encoder depth and / or for the heads
+            groups = layerwise_groups(param_optimizer, args.learning_rate, layer_decay=args.get("layerwise_lr_decay", 1.0),
+                                      head_lr=args.get("head_learning_rate"), weight_decay=0.01)
+        else:
+            groups = [
+                {"params": [p for n, p in param_optimizer if not any(nd in n for nd in no_decay)], "weight_decay": 0.01},
+                {"params": [p for n, p in param_optimizer if any(nd in n for nd in no_decay)], "weight_decay": 0.0}]
         steps = int(train_dataset_length / args.train_batch_size / args.get("gradient_accumulation_steps", 1)) * \
             args.get("num_train_epochs", 1)
         self.num_train_optimization_steps = steps

@@ -219,11 +219,14 @@ class ParameterArena(object):
         else:
             g.zero_()
 
-    def tables(self, optimise_flags, decay_flags):
-        """device int64 tables for vb_bert_adam_step / vb_refresh_bf16_shadow."""
+    def tables(self, optimise_flags, decay_flags, group_ids=None):
+        """device int64 tables for vb_bert_adam_step / vb_bert_adam_step_groups / vb_refresh_bf16_shadow.  group_ids: the
+        optimizer group of every tensor, kept in the flags word above the two flag bits (vb_bert_adam_step_groups)."""
         tens, chunks = [], []
         for i, (p, o) in enumerate(zip(self.params, self.offsets)):
             flags = (1 if optimise_flags[i] else 0) | (2 if decay_flags[i] else 0)
+            if group_ids is not None:
+                flags |= int(group_ids[i]) << 2
             tens += [o, p.numel(), o if p.dim() == 2 else -1, flags]
             n = p.numel()
             count = (n + self.CHUNK - 1) // self.CHUNK

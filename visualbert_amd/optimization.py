@@ -4,12 +4,21 @@ HIP kernel sequence over the flat parameter arena (visualbert_amd/csrc/optim.hip
 API mirrors visualbert/pytorch_pretrained_bert/optimization.py:
   _LRSchedule / ConstantLR / WarmupCosineSchedule / WarmupConstantSchedule / WarmupLinearSchedule (:37-173),
   BertAdam(params, lr, warmup, t_total, schedule, b1, b2, e, weight_decay, max_grad_norm) (:185-304).
-The device kernel evaluates the schedules the reference's training path uses -- 'warmup_linear' (the default,
-models/model_wrapper.py:136-139) and 'none' -- from its per-tensor step counters; for every other schedule
-(cosine, constant-after-warmup, the restart variants, any _LRSchedule subclass) the multiplier is evaluated on the host
-from a mirror of the (common) step count and handed to the same kernel as the learning rate of that step.
+Like the reference, BertAdam reads lr, schedule, b1, b2, e, weight_decay and max_grad_norm from EACH parameter group
+(:262-301).  The hyper-parameters travel to the kernel as a device-resident table with one row per group
+(include/visualbert_hip.h: vb_bert_adam_step_groups); a tensor's group id sits in its tensor-table entry.  The host image
+of the table is rebuilt from `param_groups` at every step() and uploaded only when it differs from the last upload, so
+`group["lr"] *= 0.5` between steps takes effect at the next step and an unchanged configuration costs no copy.
+The kernel evaluates all six schedule classes of :83-173 in double from each tensor's OWN step counter (read before
+its increment, :292,297).  Only a group whose schedule is a user subclass of _LRSchedule gets its multiplier from the
+host (`schedule.get_lr(step)`, written into the group's row every step); that needs one common step count within the
+group, which step() verifies.  When all groups share one set of hyper-parameters that the scalar entry vb_bert_adam_step can
+express -- the reference's own training set-up: groups that differ in weight decay only, warmup-linear or constant -- step()
+calls that entry instead: no table, and bit for bit the numbers this package has always given for that set-up (the scalar
+entry carries warmup and t_total in fp32).  `layerwise_groups` builds the usual fine-tuning groups (layer-wise LR decay, head LR).
 """
 import math
+import re
 
 import torch
 from torch.optim import Optimizer
@@ -107,9 +116,65 @@ _SCHEDULE_CLASSES = {c.__name__: c for c in (ConstantLR, WarmupCosineSchedule, W
                                              WarmupLinearSchedule)}
 
 
+# schedule codes of the group table (include/visualbert_hip.h: vb_bert_adam_step_groups).  Exact classes only: a subclass may
+# override get_lr_, so it is a user schedule and takes the host-multiplier code
+_DEVICE_SCHEDULES = {ConstantLR: 0, WarmupLinearSchedule: 1, WarmupConstantSchedule: 2, WarmupCosineSchedule: 3,
+                     WarmupCosineWithHardRestartsSchedule: 4, WarmupCosineWithWarmupRestartsSchedule: 5}
+_HOST_SCHEDULE = 6
+GROUP_COLS = 11         # lr, b1, b2, eps, weight_decay, max_grad_norm, schedule code, warmup, t_total, cycles, host multiplier
+
+
+def _schedule_dict(sch):
+    """what a checkpoint keeps of a schedule: the class name and its ATTRIBUTES (WarmupCosineWithWarmupRestartsSchedule holds
+    warmup * cycles in `warmup`, optimization.py:139-141) -- a plain dict, torch.save-able by either side."""
+    return {"class": type(sch).__name__, "warmup": float(getattr(sch, "warmup", -1)),
+            "t_total": float(getattr(sch, "t_total", -1)), "cycles": getattr(sch, "cycles", None)}
+
+
+def _schedule_from_dict(d):
+    """the inverse of _schedule_dict: the saved values ARE the attributes, so they are set as attributes, not passed through
+    the constructor again (which would multiply a restart schedule's warm-up by `cycles` a second time)."""
+    cls = _SCHEDULE_CLASSES[d["class"]]
+    sch = cls.__new__(cls)
+    sch.warmup, sch.t_total = float(d["warmup"]), float(d["t_total"])
+    if d.get("cycles") is not None:
+        sch.cycles = d["cycles"]
+    elif issubclass(cls, WarmupCosineSchedule):
+        sch.cycles = 0.5 if cls is WarmupCosineSchedule else 1.
+    return sch
+
+
+def layerwise_groups(named_parameters, lr, layer_decay=1.0, head_lr=None, weight_decay=0.01):
+    """Reference-style parameter groups for fine-tuning from a pre-trained encoder.  'pooler' parameters are dropped and
+    the bias / LayerNorm names get weight_decay 0, exactly as ModelWrapper.initialize_opimizer does
+    (models/model_wrapper.py:100-112).  Encoder layer i of L gets lr * layer_decay ** (L - 1 - i), the embeddings one factor
+    more (layer_decay ** L), everything outside bert.embeddings / bert.encoder (the heads) gets `head_lr or lr`.
+    Parameters with equal (lr, weight_decay) share a group, in the order of `named_parameters`: with layer_decay = 1 and no
+    head_lr the result is the two groups of initialize_opimizer."""
+    named = [(n, p) for n, p in named_parameters if "pooler" not in n]
+    no_decay = ["bias", "LayerNorm.bias", "LayerNorm.weight"]
+    layer_re = re.compile(r"(?:^|\.)bert\.encoder\.layer\.(\d+)\.")
+    layer_of = {n: int(m.group(1)) for n, m in ((n, layer_re.search(n)) for n, _ in named) if m}
+    n_layers = 1 + max(layer_of.values()) if layer_of else 0
+    groups = {}
+    for n, p in named:
+        if n in layer_of:
+            g_lr = lr * layer_decay ** (n_layers - 1 - layer_of[n])
+        elif re.search(r"(?:^|\.)bert\.embeddings\.", n):
+            g_lr = lr * layer_decay ** n_layers
+        elif re.search(r"(?:^|\.)bert\.encoder\.", n):
+            g_lr = lr                                   # encoder parameters above the layer stack
+        else:
+            g_lr = head_lr or lr
+        wd = 0.0 if any(nd in n for nd in no_decay) else weight_decay
+        groups.setdefault((g_lr, wd), {"params": [], "lr": g_lr, "weight_decay": wd})["params"].append(p)
+    return list(groups.values())
+
+
 class BertAdam(Optimizer):
     """BERT's Adam: per-tensor gradient clipping, no bias correction, decoupled weight decay, eps outside
-    the sqrt, LR schedule evaluated from a per-tensor step counter (optimization.py:239-304).
+    the sqrt, LR schedule evaluated from a per-tensor step counter (optimization.py:239-304).  Every parameter group
+    carries its own lr, schedule, b1, b2, e, weight_decay and max_grad_norm.
 
     All parameters must live in one visualbert_amd ParameterArena (every model built by
     visualbert_amd.modeling does).  State (exp_avg = 'next_m', exp_avg_sq = 'next_v', step counters)
@@ -137,22 +202,15 @@ class BertAdam(Optimizer):
             schedule = SCHEDULES[schedule](warmup=warmup, t_total=t_total)
         defaults = dict(lr=lr, schedule=schedule, b1=b1, b2=b2, e=e, weight_decay=weight_decay,
                         max_grad_norm=max_grad_norm)
-        super(BertAdam, self).__init__(params, defaults)
         self._fused = None
+        self.table_uploads = 0                           # host-to-device copies of the group table so far
+        super(BertAdam, self).__init__(params, defaults)
 
     # -- fused state -------------------------------------------------------------------------------
     def _build(self):
         arena = None
-        member = {}
-        g0 = self.param_groups[0]
+        member = {}                                      # id(parameter) -> index of its group
         for gi, group in enumerate(self.param_groups):
-            for k in ("lr", "b1", "b2", "e", "max_grad_norm"):
-                if group[k] != g0[k]:
-                    raise NotImplementedError("fused BertAdam: groups may differ in weight_decay only (as in "
-                                              "models/model_wrapper.py:108-112); %s differs" % k)
-            if type(group["schedule"]) is not type(g0["schedule"]) or \
-                    group["schedule"].warmup != g0["schedule"].warmup or group["schedule"].t_total != g0["schedule"].t_total:
-                raise NotImplementedError("fused BertAdam: one schedule for all groups")
             for p in group["params"]:
                 a = getattr(p, "_vb_arena", None)
                 if a is None:
@@ -162,27 +220,66 @@ class BertAdam(Optimizer):
                     arena = a
                 elif a is not arena:
                     raise RuntimeError("visualbert_amd.BertAdam: parameters from different arenas")
-                member[id(p)] = group["weight_decay"]
-        wds = sorted(set(v for v in member.values() if v > 0.0))
-        if len(wds) > 1:
-            raise NotImplementedError("fused BertAdam: a single non-zero weight_decay value")
-        sch = g0["schedule"]
-        if type(sch) is WarmupLinearSchedule:
-            code = 1                                     # evaluated on the device from the per-tensor step counters
-        elif type(sch) is ConstantLR or sch.t_total < 0:
-            code = 0
-        else:
-            code = -1                                    # evaluated on the host, see step()
+                member[id(p)] = gi
         opt_flags = [id(p) in member for p in arena.params]
-        dec_flags = [member.get(id(p), 0.0) > 0.0 for p in arena.params]
-        tt, ct, nt, nc = arena.tables(opt_flags, dec_flags)
+        dec_flags = [id(p) in member and self.param_groups[member[id(p)]]["weight_decay"] > 0.0 for p in arena.params]
+        group_ids = [member.get(id(p), 0) for p in arena.params]
+        tt, ct, nt, nc = arena.tables(opt_flags, dec_flags, group_ids)
         dev = arena.device
-        self._fused = dict(arena=arena, tt=tt, ct=ct, nt=nt, nc=nc, code=code, wd=wds[0] if wds else 0.0,
+        self._fused = dict(arena=arena, tt=tt, ct=ct, nt=nt, nc=nc, n_groups=len(self.param_groups), group_ids=group_ids,
                            m=torch.zeros_like(arena.data), v=torch.zeros_like(arena.data),
                            norm2=torch.zeros(nt + nc, dtype=torch.float32, device=dev),
-                           steps=torch.zeros(nt, dtype=torch.int32, device=dev), host_step=0,
-                           opt_flags=opt_flags, dec_flags=dec_flags)
+                           steps=torch.zeros(nt, dtype=torch.int32, device=dev),
+                           # the group table: its device copy and the host image that copy was made from (None: not yet)
+                           gt=torch.zeros(len(self.param_groups) * GROUP_COLS, dtype=torch.float64, device=dev), gt_host=None,
+                           opt_flags=opt_flags, dec_flags=dec_flags,
+                           group_decays=[g["weight_decay"] > 0.0 for g in self.param_groups])
         return self._fused
+
+    def _group_rows(self, f):
+        """host image of the group table, from param_groups as they are NOW."""
+        rows = []
+        steps = None
+        for gi, g in enumerate(self.param_groups):
+            sch = g["schedule"]
+            code = _DEVICE_SCHEDULES.get(type(sch), _HOST_SCHEDULE)
+            mult = 1.0
+            if code == _HOST_SCHEDULE:
+                # a user schedule is a Python object: one multiplier per group and step, from ONE step count -- the counters the
+                # device keeps per tensor must agree within the group (optimization.py:283-284 evaluates at state['step']
+                # BEFORE incrementing it)
+                if steps is None:
+                    steps = f["steps"].tolist()
+                taken = sorted(set(s for s, gid, fl in zip(steps, f["group_ids"], f["opt_flags"]) if fl and gid == gi))
+                if len(taken) > 1:
+                    raise NotImplementedError("fused BertAdam: %s is evaluated on the host from ONE step count per group, "
+                                              "the tensors of group %d are at %s" % (type(sch).__name__, gi, taken))
+                mult = float(sch.get_lr(taken[0] if taken else 0))
+            rows += [float(g["lr"]), float(g["b1"]), float(g["b2"]), float(g["e"]), float(g["weight_decay"]),
+                     float(g["max_grad_norm"]), float(code), float(getattr(sch, "warmup", 0.0)),
+                     float(getattr(sch, "t_total", -1.0)), float(getattr(sch, "cycles", 0.0) or 0.0), mult]
+        return rows
+
+    @staticmethod
+    def _one_set_of_scalars(rows, f):
+        """(lr, b1, b2, eps, weight_decay, max_grad_norm, warmup, t_total, schedule) for vb_bert_adam_step when the groups of
+        `rows` differ in weight decay only -- one non-zero value, on exactly the tensors whose decay flag (tensor table, bit 1)
+        was set when the tables were built -- and the schedule is warmup-linear or constant; else None."""
+        g0 = rows[:GROUP_COLS]
+        code, t_total = int(g0[6]), g0[8]
+        if code == _HOST_SCHEDULE or not (code in (0, 1) or t_total < 0):
+            return None
+        decays = set()
+        for gi in range(len(rows) // GROUP_COLS):
+            r = rows[gi * GROUP_COLS:(gi + 1) * GROUP_COLS]
+            if r[:4] != g0[:4] or r[5:9] != g0[5:9] or (r[4] > 0.0) != f["group_decays"][gi]:
+                return None
+            if r[4] > 0.0:
+                decays.add(r[4])
+        if len(decays) > 1:
+            return None
+        return (g0[0], g0[1], g0[2], g0[3], decays.pop() if decays else 0.0, g0[5], g0[7], t_total,
+                1 if (code == 1 and t_total >= 0) else 0)
 
     def _touched_flags(self, f):
         """The reference's step() skips a parameter whose .grad is None -- no moment update, no weight decay
@@ -199,6 +296,21 @@ class BertAdam(Optimizer):
             return synced
         return a.touched_flags()
 
+    @staticmethod
+    def _carry_state(old, f):
+        """moments and step counters follow their parameters by NAME from one fused state into a freshly built one."""
+        a0, a1 = old["arena"], f["arena"]
+        where = {n: (o, p.numel(), i) for i, (n, p, o) in enumerate(zip(a0.names, a0.params, a0.offsets))}
+        steps0, steps1 = old["steps"].tolist(), f["steps"].tolist()
+        for i, (n, p, o) in enumerate(zip(a1.names, a1.params, a1.offsets)):
+            if n not in where or where[n][1] != p.numel():
+                raise RuntimeError("visualbert_amd.BertAdam: parameter %r changed under a running optimizer" % n)
+            o0, cnt, i0 = where[n]
+            f["m"][o:o + cnt].copy_(old["m"][o0:o0 + cnt])
+            f["v"][o:o + cnt].copy_(old["v"][o0:o0 + cnt])
+            steps1[i] = steps0[i0]
+        f["steps"].copy_(torch.tensor(steps1, dtype=torch.int32))
+
     def fused(self):
         f = self._fused
         if f is None or f["arena"] is not getattr(self.param_groups[0]["params"][0], "_vb_arena", None):
@@ -207,19 +319,18 @@ class BertAdam(Optimizer):
             if old is not None and int(old["steps"].max()) > 0:
                 # the model was moved / re-laid-out after training had started (TrainVisualBERTObjective._apply rebuilds the
                 # arena): the moments and step counters follow their parameters by NAME instead of silently restarting
-                a0, a1 = old["arena"], f["arena"]
-                where = {n: (o, p.numel(), i) for i, (n, p, o) in enumerate(zip(a0.names, a0.params, a0.offsets))}
-                steps0, steps1 = old["steps"].tolist(), f["steps"].tolist()
-                for i, (n, p, o) in enumerate(zip(a1.names, a1.params, a1.offsets)):
-                    if n not in where or where[n][1] != p.numel():
-                        raise RuntimeError("visualbert_amd.BertAdam: parameter %r changed under a running optimizer" % n)
-                    o0, cnt, i0 = where[n]
-                    f["m"][o:o + cnt].copy_(old["m"][o0:o0 + cnt])
-                    f["v"][o:o + cnt].copy_(old["v"][o0:o0 + cnt])
-                    steps1[i] = steps0[i0]
-                f["steps"].copy_(torch.tensor(steps1, dtype=torch.int32))
-                f["host_step"] = old["host_step"]
+                self._carry_state(old, f)
         return f
+
+    def add_param_group(self, param_group):
+        """a group added after steps have been taken: the tables are rebuilt (the new tensors join with zero moments and a zero
+        counter), every earlier parameter keeps its moments and its counter."""
+        super(BertAdam, self).add_param_group(param_group)
+        old = getattr(self, "_fused", None)
+        if old is not None:
+            self._fused = None
+            if old["arena"] is getattr(self.param_groups[0]["params"][0], "_vb_arena", None):
+                self._carry_state(old, self._build())
 
     def zero_grad(self, set_to_none=False):
         """one memset of the flat gradient arena; .grad stays a view into it (set_to_none is ignored on
@@ -227,11 +338,15 @@ class BertAdam(Optimizer):
         self.fused()["arena"].zero_grad()
 
     def get_lr(self):
+        """one value per optimised tensor, in arena order: its own group's lr times its own group's schedule at its own step."""
         f = self.fused()
-        g = self.param_groups[0]
         steps = f["steps"].tolist()
-        flags = f["tt"].view(-1, 4)[:, 3].tolist()
-        return [g["lr"] * g["schedule"].get_lr(s) for s, fl in zip(steps, flags) if fl & 1]
+        out = []
+        for s, gid, fl in zip(steps, f["group_ids"], f["opt_flags"]):
+            if fl:
+                g = self.param_groups[gid]
+                out.append(g["lr"] * g["schedule"].get_lr(s))
+        return out
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -241,22 +356,31 @@ class BertAdam(Optimizer):
                 loss = closure()
         f = self.fused()
         a = f["arena"]
-        g = self.param_groups[0]
-        sch = g["schedule"]
         L = _lib.lib()
         touched = self._touched_flags(f)
-        lr, code = float(g["lr"]), f["code"]
-        if code < 0:
-            # every optimised tensor takes every step, so one host counter mirrors the device's per-tensor counters
-            # (optimization.py:283-284 evaluates the schedule at state['step'] BEFORE incrementing it)
-            lr, code = lr * float(sch.get_lr(f["host_step"])), 0
-        rc = L.vb_bert_adam_step(_lib.ptr(a.data), _lib.ptr(a.grad), _lib.ptr(f["m"]), _lib.ptr(f["v"]),
-                                 _lib.ptr(a.shadow), _lib.ptr(f["ct"]), f["nc"], _lib.ptr(f["tt"]), f["nt"],
-                                 _lib.ptr(touched), _lib.ptr(f["norm2"]), _lib.ptr(f["steps"]), lr, float(g["b1"]),
-                                 float(g["b2"]), float(g["e"]), float(f["wd"]), float(g["max_grad_norm"]),
-                                 float(sch.warmup), float(sch.t_total), code, _lib.stream_ptr())
-        _lib.check(rc, "vb_bert_adam_step")
-        f["host_step"] += 1
+        rows = self._group_rows(f)
+        one = self._one_set_of_scalars(rows, f)
+        if one is not None:
+            # every group shares one set of hyper-parameters the scalar entry can express (the reference's own training set-up,
+            # models/model_wrapper.py:108-139: two groups that differ in weight decay only): no table, and the numbers of every
+            # earlier release of this package, bit for bit
+            rc = L.vb_bert_adam_step(_lib.ptr(a.data), _lib.ptr(a.grad), _lib.ptr(f["m"]), _lib.ptr(f["v"]),
+                                     _lib.ptr(a.shadow), _lib.ptr(f["ct"]), f["nc"], _lib.ptr(f["tt"]), f["nt"],
+                                     _lib.ptr(touched), _lib.ptr(f["norm2"]), _lib.ptr(f["steps"]), *one,
+                                     _lib.stream_ptr())
+            _lib.check(rc, "vb_bert_adam_step")
+        else:
+            fresh = rows != f["gt_host"]
+            if fresh:                                    # first step, or a hyper-parameter was changed since the last upload
+                f["gt"].copy_(torch.tensor(rows, dtype=torch.float64))
+                f["gt_host"] = rows
+                self.table_uploads += 1
+            # the library checks the tables' contents (group ids, schedule codes) only when asked to: it has to read them back
+            rc = L.vb_bert_adam_step_groups(_lib.ptr(a.data), _lib.ptr(a.grad), _lib.ptr(f["m"]), _lib.ptr(f["v"]),
+                                            _lib.ptr(a.shadow), _lib.ptr(f["ct"]), f["nc"], _lib.ptr(f["tt"]), f["nt"],
+                                            _lib.ptr(touched), _lib.ptr(f["norm2"]), _lib.ptr(f["steps"]), _lib.ptr(f["gt"]),
+                                            f["n_groups"], 1 if fresh else 0, _lib.stream_ptr())
+            _lib.check(rc, "vb_bert_adam_step_groups")
         # the kernel refreshed the bf16 shadows of every optimised 2-D parameter
         shadowed = f.get("shadowed")
         if shadowed is None:                         # (the fused state -- and this list with it -- is rebuilt by load_state_dict)
@@ -291,17 +415,14 @@ class BertAdam(Optimizer):
                 k += 1
             gd = {kk: vv for kk, vv in group.items() if kk not in ("params", "schedule")}
             gd["params"] = ids
-            sch = group["schedule"]
-            # a plain dict, not the object and not a bare class name: torch.save-able by either side and enough to
-            # rebuild the schedule on load
-            gd["schedule"] = {"class": type(sch).__name__, "warmup": float(getattr(sch, "warmup", -1)),
-                              "t_total": float(getattr(sch, "t_total", -1)), "cycles": getattr(sch, "cycles", None)}
+            gd["schedule"] = _schedule_dict(group["schedule"])       # not the object and not a bare class name
             groups.append(gd)
         return dict(state=state, param_groups=groups)
 
     def load_state_dict(self, sd):
-        # hyper-parameters and the schedule travel with the checkpoint (saved as {"class", "warmup", "t_total", "cycles"});
-        # a checkpoint written by the reference carries the schedule OBJECT of its own module -- rebuilt here by class name
+        # hyper-parameters and the schedule travel with the checkpoint, per group (saved as {"class", "warmup", "t_total",
+        # "cycles"}, the schedule's attributes); a checkpoint written by the reference carries the schedule OBJECT of its own
+        # module -- rebuilt here by class name.  A user schedule (a class this module does not know) stays as the group has it.
         for group, saved in zip(self.param_groups, sd.get("param_groups", [])):
             for k, v in saved.items():
                 if k in ("params", "schedule"):
@@ -309,15 +430,11 @@ class BertAdam(Optimizer):
                 group[k] = v
             sch = saved.get("schedule")
             if sch is not None and not isinstance(sch, dict):
-                sch = {"class": type(sch).__name__, "warmup": float(getattr(sch, "warmup", -1)),
-                       "t_total": float(getattr(sch, "t_total", -1)), "cycles": getattr(sch, "cycles", None)}
+                sch = _schedule_dict(sch)
             if isinstance(sch, dict) and sch.get("class") in _SCHEDULE_CLASSES:
-                kw = dict(warmup=sch["warmup"], t_total=sch["t_total"])
-                if sch.get("cycles") is not None:
-                    kw["cycles"] = sch["cycles"]
-                group["schedule"] = _SCHEDULE_CLASSES[sch["class"]](**kw)
-        # the fused state caches weight decay, the decay / optimise flags and the device tables: rebuild it from the
-        # hyper-parameters just restored (the moments and counters are overwritten from the checkpoint right below)
+                group["schedule"] = _schedule_from_dict(sch)
+        # the fused state caches the group ids and the device tables: rebuild it (the moments and counters are overwritten from
+        # the checkpoint right below; the group table is re-made from the restored hyper-parameters at the next step)
         old = self._fused
         self._fused = None
         f = self.fused()
@@ -328,8 +445,6 @@ class BertAdam(Optimizer):
             f["m"].copy_(old["m"])
             f["v"].copy_(old["v"])
             f["steps"].copy_(old["steps"])
-        sch0 = self.param_groups[0]["schedule"]
-        f["code"] = 1 if type(sch0) is WarmupLinearSchedule else (0 if (type(sch0) is ConstantLR or sch0.t_total < 0) else -1)
         a = f["arena"]
         idx = {id(p): i for i, p in enumerate(a.params)}
         steps = f["steps"].tolist()
@@ -345,9 +460,3 @@ class BertAdam(Optimizer):
                     steps[i] = int(st["step"])
                 k += 1
         f["steps"].copy_(torch.tensor(steps, dtype=torch.int32))
-        flags = f["tt"].view(-1, 4)[:, 3].tolist()
-        taken = sorted(set(st for st, fl in zip(steps, flags) if fl & 1))
-        if f["code"] < 0 and len(taken) > 1:
-            raise NotImplementedError("fused BertAdam: %s is evaluated from ONE step count, the checkpoint holds %s"
-                                      % (type(self.param_groups[0]["schedule"]).__name__, taken))
-        f["host_step"] = taken[-1] if taken else 0
