@@ -306,6 +306,33 @@ int vb_bert_adam_step_groups(float* params, const float* grads, float* exp_avg, 
                              void* bf16_shadow, const int64_t* chunk_table, int n_chunks,
                              const int64_t* tensor_table, int n_tensors, const float* touched, float* norm2_ws, int* step_counters,
                              const double* group_table, int n_groups, int validate, void* stream);
+/* ------------------------------------------------------------------------------------------------
+ * Fused multi-tensor LAMB (You et al., "Large Batch Optimization for Deep Learning", NVLAMB conventions) for large-batch training,
+ * on the arena, chunk_table, tensor_table, touched, step_counters and validate of vb_bert_adam_step_groups, with exactly their
+ * meaning (skip rule, group id in flags >> 2, VB_ERR_ARG with nothing changed under validate != 0, no step for a tensor with a
+ * bad row under validate == 0).
+ * group_table: fp64[n_groups][13] = {lr, b1, b2, eps, weight_decay, max_grad_norm, schedule code, warmup, t_total, cycles,
+ * host multiplier, bias_correction (0/1), always_adapt (0/1)} -- the 11 columns of vb_bert_adam_step_groups, then two more.
+ * ws: fp32[vb_lamb_ws_floats(n_tensors, n_chunks)] scratch: per-chunk and per-tensor scalars only (-1: bad counts).
+ * Per tensor that takes the step, s = its counter before the increment, t = s + 1:
+ *   gnorm = sqrt(sum of ||g||^2 over ALL tensors that take the step, every group)
+ *   c     = max_grad_norm > 0 ? min(1, max_grad_norm / (gnorm + 1e-6)) : 1              (the group's own max_grad_norm)
+ *   g'    = g c ;  m = b1 m + (1 - b1) g' ;  v = b2 v + (1 - b2) g'^2
+ *   mh, vh = bias_correction ? (m / (1 - b1^t), v / (1 - b2^t)) : (m, v)
+ *   u     = mh / (sqrt(vh) + eps) + weight_decay p
+ *   r     = (weight_decay <= 0 and not always_adapt) ? 1 : (||p|| > 0 and ||u|| > 0 ? ||p|| / ||u|| : 1)   (p before the update)
+ *   p    -= lr schedule(s) r u ;  bf16 shadow refreshed ;  counter += 1
+ * Every norm is summed without atomics, in table order: two launches on the same data give the same bits.  grads is only read.
+ * No arena-sized scratch: u is formed twice (for its norm, then to be applied) from the stored m, v and the old p.
+ * The element arithmetic and its order are those of vb_bert_adam_step_groups: with bias_correction = always_adapt = 0, every
+ * weight_decay = 0 and max_grad_norm <= 0 the two entries give bit-identical params, moments, shadow and counters on one table.
+ * validate == 0: no host<->device traffic, nothing allocated, everything enqueued on `stream`.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t vb_lamb_ws_floats(int n_tensors, int n_chunks);
+int vb_lamb_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, void* bf16_shadow,
+                        const int64_t* chunk_table, int n_chunks, const int64_t* tensor_table, int n_tensors,
+                        const float* touched, float* ws, int* step_counters,
+                        const double* group_table, int n_groups, int validate, void* stream);
 int vb_refresh_bf16_shadow(const float* params, void* bf16_shadow, const int64_t* chunk_table,
                            int n_chunks, const int64_t* tensor_table, void* stream);
 /* W^T copies of the bf16 GEMM weights (so dgrad dx = dy W is a K-contiguous x K-contiguous GEMM):

@@ -1,4 +1,4 @@
-// optim.hip -- fused multi-tensor BertAdam over the flat parameter arena.
+// optim.hip -- fused multi-tensor optimizers over the flat parameter arena: BertAdam (below) and LAMB (vb_lamb_step_groups).
 //
 // Replaces BertAdam.step (pytorch_pretrained_bert/optimization.py:239-304), a Python loop over ~200
 // tensors with ~10 small kernels each, by three launches over one contiguous fp32 arena:
@@ -14,6 +14,20 @@
 // host<->device traffic per step, so the step can sit in a captured graph.
 // Two entries share the element loop: vb_bert_adam_step (one set of scalar hyper-parameters) and
 // vb_bert_adam_step_groups (a device-resident table with one row per parameter group, :262-301).
+//
+// vb_lamb_step_groups -- LAMB (You et al., "Large Batch Optimization for Deep Learning", with the NVLAMB conventions: one GLOBAL
+// gradient norm, optional bias correction, trust ratio per tensor) on the same arena, tables, group table (+ 2 columns), skip
+// rule and norm kernels.  The trust ratio ||p|| / ||u|| of a tensor is known only after every element's update u is, so the
+// element work is two passes, and u is RECOMPUTED in the second from the new moments instead of being kept in an arena-sized buffer:
+//   1. per-tensor gradient sums of squares (the BertAdam kernels), then ONE wave adds them in table order: the global norm
+//   2. moments: m, v updated and stored; u formed in registers; per-chunk partials of ||p||^2 and ||u||^2
+//   3. per-tensor trust ratios from the partials, in table order
+//   4. apply: u again from the stored m, v and the old p; p -= lr * schedule(step) * ratio * u; bf16 shadow
+//   5. step counters += 1
+// HBM traffic per parameter: pass 2 reads g, m, v, p (16 B) + writes m, v (8 B); pass 4 reads m, v, p (12 B) + writes p (4 B)
+// [+ 2 B shadow] = 40-42 B, counted like BertAdam's 28-30 B (the norm pass adds 4 B to either).  A tensor whose ratio is 1 by rule
+// (no weight decay, not always_adapt) skips the read of p in pass 2.  With bias_correction = always_adapt = 0, no weight decay and no
+// clipping the result is bit for bit that of vb_bert_adam_step_groups: the element arithmetic is adam_update_chunk's, in its order.
 #include "vb_rt.h"
 #include "../../include/visualbert_hip.h"
 
@@ -153,12 +167,13 @@ enum { SCHED_NONE = 0, SCHED_WARMUP_LINEAR, SCHED_WARMUP_CONSTANT, SCHED_WARMUP_
 
 // the row of tensor `tid`, or NULL when the tensor takes no part: not optimised, or -- only reachable when the caller passed
 // validate = 0 with a bad table -- a group id outside the table or an unknown schedule code (never read outside the table)
-VB_DEVICE const double* adam_group_row(const int64_t* tensors, long tid, const double* groups, int n_groups) {
+VB_DEVICE const double* adam_group_row(const int64_t* tensors, long tid, const double* groups, int n_groups,
+                                       int cols = GROUP_COLS) {
     const long flags = tensors[tid * 4 + 3];
     if (!(flags & 1)) return nullptr;
     const long gid = flags >> 2;
     if (gid < 0 || gid >= n_groups) return nullptr;
-    const double* row = groups + gid * GROUP_COLS;
+    const double* row = groups + gid * cols;
     const double code = row[G_SCHED];
     if (!(code >= 0.0 && code < (double)SCHED_COUNT) || code != (double)(int)code) return nullptr;
     return row;
@@ -229,18 +244,18 @@ VB_KERNEL adam_step_inc_groups_kernel(int* steps, const int64_t* tensors, int n,
 // argument check of the device-resident tables: they are read back (this waits for the stream), so the caller asks for it only
 // when a table is new
 static int adam_groups_validate(const int64_t* tensor_table, int n_tensors, const double* group_table, int n_groups,
-                                hipStream_t s) {
+                                hipStream_t s, int cols = GROUP_COLS) {
     int64_t* tt = (int64_t*)malloc((size_t)n_tensors * 4 * sizeof(int64_t));
-    double* gt = (double*)malloc((size_t)n_groups * GROUP_COLS * sizeof(double));
+    double* gt = (double*)malloc((size_t)n_groups * cols * sizeof(double));
     int rc = (tt && gt) ? VB_OK : VB_ERR_LAUNCH;
 #ifdef VB_EMU
     if (rc == VB_OK) {
         memcpy(tt, tensor_table, (size_t)n_tensors * 4 * sizeof(int64_t));
-        memcpy(gt, group_table, (size_t)n_groups * GROUP_COLS * sizeof(double));
+        memcpy(gt, group_table, (size_t)n_groups * cols * sizeof(double));
     }
 #else
     if (rc == VB_OK && (hipMemcpyAsync(tt, tensor_table, (size_t)n_tensors * 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                        hipMemcpyAsync(gt, group_table, (size_t)n_groups * GROUP_COLS * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess ||
+                        hipMemcpyAsync(gt, group_table, (size_t)n_groups * cols * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess ||
                         hipStreamSynchronize(s) != hipSuccess))
         rc = VB_ERR_LAUNCH;
 #endif
@@ -249,12 +264,166 @@ static int adam_groups_validate(const int64_t* tensor_table, int n_tensors, cons
         if ((flags & 1) && ((flags >> 2) < 0 || (flags >> 2) >= n_groups)) rc = VB_ERR_ARG;
     }
     for (int g = 0; rc == VB_OK && g < n_groups; ++g) {
-        const double code = gt[(size_t)g * GROUP_COLS + G_SCHED];
+        const double code = gt[(size_t)g * cols + G_SCHED];
         if (!(code >= 0.0 && code < (double)SCHED_COUNT) || code != (double)(int)code) rc = VB_ERR_ARG;
     }
     free(tt);
     free(gt);
     return rc;
+}
+
+// ---- LAMB (vb_lamb_step_groups) ------------------------------------------------------------------------------------------
+// group table row (fp64 x LAMB_COLS): the GROUP_COLS columns above in the same order, then bias_correction (0/1) and
+// always_adapt (0/1).  workspace (fp32): per-tensor ||g||^2 [n_tensors] | per-tensor trust ratio [n_tensors] | global ||g||^2
+// [4, one used] | per-chunk partials of ||g||^2, ||p||^2, ||u||^2 [3 x n_chunks].  Every sum is formed without atomics: a chunk's
+// partial has its own slot and one wave adds a tensor's (or the table's) slots in table order -- the reason given at chunk_norm2.
+constexpr int LAMB_COLS = GROUP_COLS + 2;
+enum { L_BIAS_CORRECTION = GROUP_COLS, L_ALWAYS_ADAPT };
+
+// the row of a tensor that takes this step, or NULL (not optimised, bad row under validate = 0, or skipped by adam_skips)
+VB_DEVICE const double* lamb_row(const int64_t* tensors, long tid, const double* groups, int n_groups, const float* touched,
+                                 const float* norm2, const int* steps) {
+    const double* row = adam_group_row(tensors, tid, groups, n_groups, LAMB_COLS);
+    if (!row || adam_skips(touched, norm2, steps, tid)) return nullptr;
+    return row;
+}
+
+// every optimised tensor's norm is needed: the clip coefficient comes from the norm over ALL groups
+VB_KERNEL VB_LAUNCH_BOUNDS(NT) lamb_norm_kernel(const float* grads, const int64_t* chunks, const int64_t* tensors,
+                                               const double* groups, int n_groups, float* partial) {
+    VB_DYN_SMEM(smem);
+    const int64_t* c = chunks + (long)blockIdx.x * 4;
+    if (!adam_group_row(tensors, c[0], groups, n_groups, LAMB_COLS)) {
+        if (threadIdx.x == 0) partial[blockIdx.x] = 0.f;
+        return;
+    }
+    chunk_norm2(grads, c, (float*)smem, partial + blockIdx.x);
+}
+
+// one wave: lane l adds the norms of tensors l, l + 64, ... that take this step, then the fixed butterfly
+VB_KERNEL VB_LAUNCH_BOUNDS(64) lamb_global_norm_kernel(const int64_t* tensors, int n_tensors, const double* groups, int n_groups,
+                                                      const float* touched, const float* norm2, const int* steps, float* gnorm2) {
+    float s = 0.f;
+    for (int t = threadIdx.x; t < n_tensors; t += 64)
+        if (lamb_row(tensors, t, groups, n_groups, touched, norm2, steps)) s += norm2[t];
+    s = wave_sum(s);
+    if (threadIdx.x == 0) *gnorm2 = s;
+}
+
+struct LambHyper { float b1, b2, eps, wd, c1, c2; bool bias_correction; };
+
+VB_DEVICE LambHyper lamb_hyper(const double* row, int step) {
+    LambHyper h;
+    h.b1 = (float)row[G_B1]; h.b2 = (float)row[G_B2]; h.eps = (float)row[G_EPS]; h.wd = (float)row[G_WD];
+    h.bias_correction = row[L_BIAS_CORRECTION] != 0.0;
+    h.c1 = h.c2 = 1.0f;
+    if (h.bias_correction) {                         // 1 - beta^t of the fp32 betas the element loop uses, t = step + 1
+        h.c1 = (float)(1.0 - pow((double)h.b1, (double)(step + 1)));
+        h.c2 = (float)(1.0 - pow((double)h.b2, (double)(step + 1)));
+    }
+    return h;
+}
+
+// the update direction of one element from its NEW moments and its OLD parameter: adam_update_chunk's expression, with the
+// moments divided by 1 - beta^t first when the group asks for bias correction.  Both element passes call this, so the u whose
+// norm sets the trust ratio and the u that is applied are the same bits.
+VB_DEVICE float lamb_direction(float mm, float vv, float p, const LambHyper& h) {
+    if (h.bias_correction) { mm = mm / h.c1; vv = vv / h.c2; }
+    float u = mm / (sqrtf(vv) + h.eps);
+    if (h.wd > 0.f) u += h.wd * p;
+    return u;
+}
+
+// the trust ratio is 1 by rule for a tensor without weight decay unless its group adapts always: no norm is formed for it
+VB_DEVICE bool lamb_adapts(const double* row) { return (float)row[G_WD] > 0.f || row[L_ALWAYS_ADAPT] != 0.0; }
+
+// pass 2: moments of one chunk (4-byte accesses as in adam_update_chunk) + this chunk's partials of ||p||^2 and ||u||^2
+// (the four arena buffers never overlap: __restrict__ lets the loads of the next trip start before this trip's stores)
+VB_KERNEL VB_LAUNCH_BOUNDS(NT) lamb_moments_kernel(const float* __restrict__ params, const float* __restrict__ grads,
+                                                  float* __restrict__ m, float* __restrict__ v,
+                                                  const int64_t* chunks, const int64_t* tensors, const float* norm2,
+                                                  const float* gnorm2, const int* steps, const float* touched,
+                                                  const double* groups, int n_groups, float* partial_p, float* partial_u) {
+    VB_DYN_SMEM(smem);
+    float* red = (float*)smem;                                       // [2][4]
+    const int64_t* c = chunks + (long)blockIdx.x * 4;
+    const long tid = c[0], off = c[1], len = c[2];
+    const double* row = lamb_row(tensors, tid, groups, n_groups, touched, norm2, steps);
+    if (!row) {
+        if (threadIdx.x == 0) { partial_p[blockIdx.x] = 0.f; partial_u[blockIdx.x] = 0.f; }
+        return;
+    }
+    const LambHyper h = lamb_hyper(row, steps[tid]);
+    const float max_grad_norm = (float)row[G_CLIP];
+    float clip = 1.0f;
+    if (max_grad_norm > 0.f) {
+        const float cc = max_grad_norm / (sqrtf(*gnorm2) + 1e-6f);
+        clip = cc < 1.0f ? cc : 1.0f;
+    }
+    const bool adapts = lamb_adapts(row);
+    float sp = 0.f, su = 0.f;
+    for (long i = threadIdx.x; i < len; i += NT) {
+        const long e = off + i;
+        const float g = grads[e] * clip;
+        const float mm = m[e] * h.b1 + (1.0f - h.b1) * g;
+        const float vv = v[e] * h.b2 + (1.0f - h.b2) * g * g;
+        m[e] = mm; v[e] = vv;
+        if (adapts) {
+            const float p = params[e];
+            const float u = lamb_direction(mm, vv, p, h);
+            sp += p * p; su += u * u;
+        }
+    }
+    sp = wave_sum(sp); su = wave_sum(su);
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = sp; red[4 + (threadIdx.x >> 6)] = su; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial_p[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+        partial_u[blockIdx.x] = (red[4] + red[5]) + (red[6] + red[7]);
+    }
+}
+
+// pass 3: one wave per tensor, as adam_norm_finish_kernel.  A tensor that formed no norms has zero partials: ratio 1.
+VB_KERNEL VB_LAUNCH_BOUNDS(64) lamb_ratio_kernel(const int64_t* chunks, int n_chunks, const float* partial_p,
+                                                const float* partial_u, float* ratio) {
+    const int j = blockIdx.x;
+    const int64_t id = chunks[(long)j * 4];
+    if (j > 0 && chunks[(long)(j - 1) * 4] == id) return;
+    const int count = (int)chunks[(long)j * 4 + 3];
+    float sp = 0.f, su = 0.f;
+    for (int k = threadIdx.x; k < count; k += 64) { sp += partial_p[j + k]; su += partial_u[j + k]; }
+    sp = wave_sum(sp); su = wave_sum(su);
+    if (threadIdx.x == 0) ratio[id] = (sp > 0.f && su > 0.f) ? sqrtf(sp) / sqrtf(su) : 1.0f;
+}
+
+// pass 4: the direction again from the stored moments, applied with the tensor's ratio
+VB_KERNEL VB_LAUNCH_BOUNDS(NT) lamb_apply_kernel(float* __restrict__ params, const float* __restrict__ m,
+                                                const float* __restrict__ v, bf16* __restrict__ shadow,
+                                                const int64_t* chunks, const int64_t* tensors, const float* norm2,
+                                                const float* ratio, const int* steps, const float* touched,
+                                                const double* groups, int n_groups) {
+    const int64_t* c = chunks + (long)blockIdx.x * 4;
+    const long tid = c[0], off = c[1], len = c[2];
+    const double* row = lamb_row(tensors, tid, groups, n_groups, touched, norm2, steps);
+    if (!row) return;
+    const int64_t* te = tensors + tid * 4;
+    const long t_off = te[0], sh_off = te[2];
+    const LambHyper h = lamb_hyper(row, steps[tid]);
+    const float lr = (float)row[G_LR] * (float)schedule_mult_group(row, steps[tid]) * ratio[tid];
+    for (long i = threadIdx.x; i < len; i += NT) {
+        const long e = off + i;
+        const float p = params[e];
+        const float u = lamb_direction(m[e], v[e], p, h);
+        const float pn = p - lr * u;
+        params[e] = pn;
+        if (shadow && sh_off >= 0) shadow[sh_off + (e - t_off)] = (bf16)pn;
+    }
+}
+
+VB_KERNEL lamb_step_inc_kernel(int* steps, const int64_t* tensors, int n, const float* touched, const float* norm2,
+                               const double* groups, int n_groups) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && lamb_row(tensors, i, groups, n_groups, touched, norm2, steps)) steps[i] += 1;
 }
 
 VB_KERNEL VB_LAUNCH_BOUNDS(NT) shadow_refresh_kernel(const float* params, bf16* shadow, const int64_t* chunks,
@@ -365,6 +534,49 @@ extern "C" int vb_bert_adam_step_groups(float* params, const float* grads, float
               group_table, n_groups);
     VB_LAUNCH(adam_step_inc_groups_kernel, dim3((unsigned)((n_tensors + 63) / 64)), dim3(64), 0, s, step_counters,
               tensor_table, n_tensors, touched, (const float*)norm2_ws, group_table, n_groups);
+    return vb_check_launch();
+}
+
+extern "C" int64_t vb_lamb_ws_floats(int n_tensors, int n_chunks) {
+    if (n_tensors <= 0 || n_chunks <= 0) return -1;
+    return 2 * (int64_t)n_tensors + 4 + 3 * (int64_t)n_chunks;
+}
+
+extern "C" int vb_lamb_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, void* bf16_shadow,
+                                   const int64_t* chunk_table, int n_chunks, const int64_t* tensor_table, int n_tensors,
+                                   const float* touched, float* ws, int* step_counters, const double* group_table,
+                                   int n_groups, int validate, void* stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !chunk_table || !tensor_table || !ws || !step_counters)
+        return VB_ERR_ARG;
+    if (n_chunks <= 0 || n_tensors <= 0 || !group_table || n_groups <= 0) return VB_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    if (validate) {
+        const int rc = adam_groups_validate(tensor_table, n_tensors, group_table, n_groups, s, LAMB_COLS);
+        if (rc != VB_OK) return rc;
+    }
+    float* norm2 = ws;                                      // [n_tensors]
+    float* ratio = norm2 + n_tensors;                       // [n_tensors]
+    float* gnorm2 = ratio + n_tensors;                      // [4]
+    float* partial_g = gnorm2 + 4;                          // [n_chunks] each
+    float* partial_p = partial_g + n_chunks;
+    float* partial_u = partial_p + n_chunks;
+    const int* steps = step_counters;
+    VB_LAUNCH(lamb_norm_kernel, dim3((unsigned)n_chunks), dim3(NT), 64, s, grads, chunk_table, tensor_table, group_table,
+              n_groups, partial_g);
+    VB_LAUNCH(adam_norm_finish_kernel, dim3((unsigned)n_chunks), dim3(64), 0, s, chunk_table, n_chunks,
+              (const float*)partial_g, norm2);
+    VB_LAUNCH(lamb_global_norm_kernel, dim3(1), dim3(64), 0, s, tensor_table, n_tensors, group_table, n_groups, touched,
+              (const float*)norm2, steps, gnorm2);
+    VB_LAUNCH(lamb_moments_kernel, dim3((unsigned)n_chunks), dim3(NT), 64, s, (const float*)params, grads, exp_avg,
+              exp_avg_sq, chunk_table, tensor_table, (const float*)norm2, (const float*)gnorm2, steps, touched, group_table,
+              n_groups, partial_p, partial_u);
+    VB_LAUNCH(lamb_ratio_kernel, dim3((unsigned)n_chunks), dim3(64), 0, s, chunk_table, n_chunks, (const float*)partial_p,
+              (const float*)partial_u, ratio);
+    VB_LAUNCH(lamb_apply_kernel, dim3((unsigned)n_chunks), dim3(NT), 0, s, params, (const float*)exp_avg,
+              (const float*)exp_avg_sq, (bf16*)bf16_shadow, chunk_table, tensor_table, (const float*)norm2,
+              (const float*)ratio, steps, touched, group_table, n_groups);
+    VB_LAUNCH(lamb_step_inc_kernel, dim3((unsigned)((n_tensors + 63) / 64)), dim3(64), 0, s, step_counters, tensor_table,
+              n_tensors, touched, (const float*)norm2, group_table, n_groups);
     return vb_check_launch();
 }
 

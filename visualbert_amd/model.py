@@ -15,7 +15,7 @@ from torch import nn
 
 from . import ops
 from .modeling import BertConfig, TrainVisualBERTObjective
-from .optimization import BertAdam, layerwise_groups
+from .optimization import BertAdam, Lamb, layerwise_groups
 
 
 class VisualBERTFixedImageEmbedding(nn.Module):
@@ -256,7 +256,17 @@ class ModelWrapper(object):
         steps = int(train_dataset_length / args.train_batch_size / args.get("gradient_accumulation_steps", 1)) * \
             args.get("num_train_epochs", 1)
         self.num_train_optimization_steps = steps
-        self.optimizer = BertAdam(groups, lr=args.learning_rate, warmup=args.warmup_proportion, t_total=steps)
+        # `optimizer` (not in the reference's configs): "bert_adam", the reference's recipe and the default, or "lamb" for
+        # large-batch training, with the optional keys `lamb_bias_correction` and `lamb_always_adapt`
+        kind = args.get("optimizer", "bert_adam")
+        if kind == "bert_adam":
+            self.optimizer = BertAdam(groups, lr=args.learning_rate, warmup=args.warmup_proportion, t_total=steps)
+        elif kind == "lamb":
+            self.optimizer = Lamb(groups, lr=args.learning_rate, warmup=args.warmup_proportion, t_total=steps,
+                                  bias_correction=args.get("lamb_bias_correction", True),
+                                  always_adapt=args.get("lamb_always_adapt", False))
+        else:
+            raise ValueError("optimizer: %r is not one of 'bert_adam', 'lamb'" % (kind,))
 
     # -- checkpoints: the reference's file names and dictionary keys (models/model_wrapper.py:150-221,
     #    utils/pytorch_misc.py:110-330), so that a run can be resumed by either side ------------------------------------

@@ -16,6 +16,11 @@ group, which step() verifies.  When all groups share one set of hyper-parameters
 express -- the reference's own training set-up: groups that differ in weight decay only, warmup-linear or constant -- step()
 calls that entry instead: no table, and bit for bit the numbers this package has always given for that set-up (the scalar
 entry carries warmup and t_total in fp32).  `layerwise_groups` builds the usual fine-tuning groups (layer-wise LR decay, head LR).
+
+`Lamb` is the optimizer for large-batch training (You et al., "Large Batch Optimization for Deep Learning", with the NVLAMB
+conventions): one global gradient-norm clip, optional bias correction, a trust ratio ||p|| / ||u|| per tensor.  It is BertAdam's
+machinery -- arena, tables, group table, schedules, `touched` hand-over, state carry-over -- around another kernel entry
+(include/visualbert_hip.h: vb_lamb_step_groups), whose group rows carry two more columns.
 """
 import math
 import re
@@ -122,6 +127,7 @@ _DEVICE_SCHEDULES = {ConstantLR: 0, WarmupLinearSchedule: 1, WarmupConstantSched
                      WarmupCosineWithHardRestartsSchedule: 4, WarmupCosineWithWarmupRestartsSchedule: 5}
 _HOST_SCHEDULE = 6
 GROUP_COLS = 11         # lr, b1, b2, eps, weight_decay, max_grad_norm, schedule code, warmup, t_total, cycles, host multiplier
+LAMB_GROUP_COLS = 13    # ... + bias_correction, always_adapt (include/visualbert_hip.h: vb_lamb_step_groups)
 
 
 def _schedule_dict(sch):
@@ -186,6 +192,21 @@ class BertAdam(Optimizer):
     torch >= 2's zero_grad(set_to_none=True) the reference itself would skip it again; `zero_grad()` here is one memset of
     the gradient arena either way.  load_state_dict keeps the moments / counters of parameters the checkpoint omits."""
 
+    # what a subclass with another kernel entry (Lamb) changes: the width of a group row and the checkpoint names of the moments
+    _group_cols = GROUP_COLS
+    _moment_keys = ("next_m", "next_v")
+
+    def _extra_defaults(self, kwargs):
+        """per-group hyper-parameters beyond BertAdam's own."""
+        return {}
+
+    def _extra_columns(self, group):
+        """the columns of a group's table row after the GROUP_COLS common ones."""
+        return []
+
+    def _ws_floats(self, nt, nc):
+        return nt + nc
+
     def __init__(self, params, lr=None, warmup=-1, t_total=-1, schedule='warmup_linear', b1=0.9, b2=0.999, e=1e-6,
                  weight_decay=0.01, max_grad_norm=1.0, **kwargs):
         if lr is None or lr < 0.0:
@@ -202,6 +223,7 @@ class BertAdam(Optimizer):
             schedule = SCHEDULES[schedule](warmup=warmup, t_total=t_total)
         defaults = dict(lr=lr, schedule=schedule, b1=b1, b2=b2, e=e, weight_decay=weight_decay,
                         max_grad_norm=max_grad_norm)
+        defaults.update(self._extra_defaults(kwargs))
         self._fused = None
         self.table_uploads = 0                           # host-to-device copies of the group table so far
         super(BertAdam, self).__init__(params, defaults)
@@ -214,12 +236,12 @@ class BertAdam(Optimizer):
             for p in group["params"]:
                 a = getattr(p, "_vb_arena", None)
                 if a is None:
-                    raise RuntimeError("visualbert_amd.BertAdam: parameter is not arena-managed (build the model "
-                                       "with visualbert_amd.modeling; no per-tensor fallback exists)")
+                    raise RuntimeError("visualbert_amd.%s: parameter is not arena-managed (build the model with "
+                                       "visualbert_amd.modeling; no per-tensor fallback exists)" % type(self).__name__)
                 if arena is None:
                     arena = a
                 elif a is not arena:
-                    raise RuntimeError("visualbert_amd.BertAdam: parameters from different arenas")
+                    raise RuntimeError("visualbert_amd.%s: parameters from different arenas" % type(self).__name__)
                 member[id(p)] = gi
         opt_flags = [id(p) in member for p in arena.params]
         dec_flags = [id(p) in member and self.param_groups[member[id(p)]]["weight_decay"] > 0.0 for p in arena.params]
@@ -228,10 +250,11 @@ class BertAdam(Optimizer):
         dev = arena.device
         self._fused = dict(arena=arena, tt=tt, ct=ct, nt=nt, nc=nc, n_groups=len(self.param_groups), group_ids=group_ids,
                            m=torch.zeros_like(arena.data), v=torch.zeros_like(arena.data),
-                           norm2=torch.zeros(nt + nc, dtype=torch.float32, device=dev),
+                           norm2=torch.zeros(self._ws_floats(nt, nc), dtype=torch.float32, device=dev),
                            steps=torch.zeros(nt, dtype=torch.int32, device=dev),
                            # the group table: its device copy and the host image that copy was made from (None: not yet)
-                           gt=torch.zeros(len(self.param_groups) * GROUP_COLS, dtype=torch.float64, device=dev), gt_host=None,
+                           gt=torch.zeros(len(self.param_groups) * self._group_cols, dtype=torch.float64, device=dev),
+                           gt_host=None,
                            opt_flags=opt_flags, dec_flags=dec_flags,
                            group_decays=[g["weight_decay"] > 0.0 for g in self.param_groups])
         return self._fused
@@ -258,6 +281,7 @@ class BertAdam(Optimizer):
             rows += [float(g["lr"]), float(g["b1"]), float(g["b2"]), float(g["e"]), float(g["weight_decay"]),
                      float(g["max_grad_norm"]), float(code), float(getattr(sch, "warmup", 0.0)),
                      float(getattr(sch, "t_total", -1.0)), float(getattr(sch, "cycles", 0.0) or 0.0), mult]
+            rows += self._extra_columns(g)
         return rows
 
     @staticmethod
@@ -348,17 +372,19 @@ class BertAdam(Optimizer):
                 out.append(g["lr"] * g["schedule"].get_lr(s))
         return out
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        f = self.fused()
+    def _upload_table(self, f, rows):
+        """the device copy of the group table follows its host image; True when it had to be copied (first step, or a
+        hyper-parameter was changed since the last upload)."""
+        fresh = rows != f["gt_host"]
+        if fresh:
+            f["gt"].copy_(torch.tensor(rows, dtype=torch.float64))
+            f["gt_host"] = rows
+            self.table_uploads += 1
+        return fresh
+
+    def _launch(self, f, touched, rows):
         a = f["arena"]
         L = _lib.lib()
-        touched = self._touched_flags(f)
-        rows = self._group_rows(f)
         one = self._one_set_of_scalars(rows, f)
         if one is not None:
             # every group shares one set of hyper-parameters the scalar entry can express (the reference's own training set-up,
@@ -370,17 +396,24 @@ class BertAdam(Optimizer):
                                      _lib.stream_ptr())
             _lib.check(rc, "vb_bert_adam_step")
         else:
-            fresh = rows != f["gt_host"]
-            if fresh:                                    # first step, or a hyper-parameter was changed since the last upload
-                f["gt"].copy_(torch.tensor(rows, dtype=torch.float64))
-                f["gt_host"] = rows
-                self.table_uploads += 1
+            fresh = self._upload_table(f, rows)
             # the library checks the tables' contents (group ids, schedule codes) only when asked to: it has to read them back
             rc = L.vb_bert_adam_step_groups(_lib.ptr(a.data), _lib.ptr(a.grad), _lib.ptr(f["m"]), _lib.ptr(f["v"]),
                                             _lib.ptr(a.shadow), _lib.ptr(f["ct"]), f["nc"], _lib.ptr(f["tt"]), f["nt"],
                                             _lib.ptr(touched), _lib.ptr(f["norm2"]), _lib.ptr(f["steps"]), _lib.ptr(f["gt"]),
                                             f["n_groups"], 1 if fresh else 0, _lib.stream_ptr())
             _lib.check(rc, "vb_bert_adam_step_groups")
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        f = self.fused()
+        a = f["arena"]
+        touched = self._touched_flags(f)
+        self._launch(f, touched, self._group_rows(f))
         # the kernel refreshed the bf16 shadows of every optimised 2-D parameter
         shadowed = f.get("shadowed")
         if shadowed is None:                         # (the fused state -- and this list with it -- is rebuilt by load_state_dict)
@@ -409,8 +442,8 @@ class BertAdam(Optimizer):
             for p in group["params"]:
                 i = idx[id(p)]
                 o, n = a.offsets[i], p.numel()
-                state[k] = dict(step=steps[i], next_m=f["m"][o:o + n].view(p.shape).clone(),
-                                next_v=f["v"][o:o + n].view(p.shape).clone())
+                state[k] = {"step": steps[i], self._moment_keys[0]: f["m"][o:o + n].view(p.shape).clone(),
+                            self._moment_keys[1]: f["v"][o:o + n].view(p.shape).clone()}
                 ids.append(k)
                 k += 1
             gd = {kk: vv for kk, vv in group.items() if kk not in ("params", "schedule")}
@@ -455,8 +488,51 @@ class BertAdam(Optimizer):
                 if st is not None:
                     i = idx[id(p)]
                     o, n = a.offsets[i], p.numel()
-                    f["m"][o:o + n].view(p.shape).copy_(st["next_m"])
-                    f["v"][o:o + n].view(p.shape).copy_(st["next_v"])
+                    f["m"][o:o + n].view(p.shape).copy_(st[self._moment_keys[0]])
+                    f["v"][o:o + n].view(p.shape).copy_(st[self._moment_keys[1]])
                     steps[i] = int(st["step"])
                 k += 1
         f["steps"].copy_(torch.tensor(steps, dtype=torch.int32))
+
+
+class Lamb(BertAdam):
+    """LAMB for large-batch training (You et al., "Large Batch Optimization for Deep Learning", NVLAMB conventions), as one fused
+    multi-tensor kernel sequence over the parameter arena (vb_lamb_step_groups).  Per step: every gradient is scaled by
+    min(1, max_grad_norm / global norm) -- ONE norm over all optimised tensors of all groups, each group applying its own
+    max_grad_norm to it; Adam moments with (bias_correction) or without division by 1 - beta^t; update u = m / (sqrt(v) + e) +
+    weight_decay * p; and every tensor moves by lr * schedule(step) * r * u with its own trust ratio r = ||p|| / ||u|| (1 when
+    either norm is 0, and 1 for a tensor without weight decay unless always_adapt).
+
+    Every key is per parameter group, schedules (objects, or user subclasses evaluated on the host) and the `.grad is None` rule
+    work as in BertAdam, and so do zero_grad, get_lr (lr x schedule; the trust ratio lives on the device), add_param_group, the
+    carry-over of state when the arena is rebuilt, and the hand-over of `touched` flags under DataParallelGradSync.  Gradients are
+    only read.  state_dict keeps {'step', 'exp_avg', 'exp_avg_sq'} per parameter and each group's hyper-parameters with its
+    schedule as a dict."""
+
+    _group_cols = LAMB_GROUP_COLS
+    _moment_keys = ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, params, lr=1e-3, warmup=-1, t_total=-1, schedule='warmup_linear', b1=0.9, b2=0.999, e=1e-6,
+                 weight_decay=0.01, max_grad_norm=1.0, bias_correction=True, always_adapt=False):
+        super(Lamb, self).__init__(params, lr=lr, warmup=warmup, t_total=t_total, schedule=schedule, b1=b1, b2=b2, e=e,
+                                   weight_decay=weight_decay, max_grad_norm=max_grad_norm, bias_correction=bias_correction,
+                                   always_adapt=always_adapt)
+
+    def _extra_defaults(self, kwargs):
+        return dict(bias_correction=bool(kwargs["bias_correction"]), always_adapt=bool(kwargs["always_adapt"]))
+
+    def _extra_columns(self, group):
+        return [1.0 if group["bias_correction"] else 0.0, 1.0 if group["always_adapt"] else 0.0]
+
+    def _ws_floats(self, nt, nc):
+        return int(_lib.lib().vb_lamb_ws_floats(nt, nc))
+
+    def _launch(self, f, touched, rows):
+        a = f["arena"]
+        fresh = self._upload_table(f, rows)
+        # as in BertAdam: the library reads the tables back to check them only when they are new
+        rc = _lib.lib().vb_lamb_step_groups(_lib.ptr(a.data), _lib.ptr(a.grad), _lib.ptr(f["m"]), _lib.ptr(f["v"]),
+                                            _lib.ptr(a.shadow), _lib.ptr(f["ct"]), f["nc"], _lib.ptr(f["tt"]), f["nt"],
+                                            _lib.ptr(touched), _lib.ptr(f["norm2"]), _lib.ptr(f["steps"]), _lib.ptr(f["gt"]),
+                                            f["n_groups"], 1 if fresh else 0, _lib.stream_ptr())
+        _lib.check(rc, "vb_lamb_step_groups")
