@@ -433,6 +433,26 @@ int vb_bert_layer_bwd(int dtype, const void* h_in, const void* h_out, const floa
                       const void* const* weights_t, const int64_t* ld_t,
                       int B, int S, int H, int I, int nh, float p_hidden, float p_attn,
                       uint64_t seed, uint32_t sid, void* stream);
+/* The same backward for a d_out that is zero outside a KNOWN set of rows -- the last encoder layer under heads that read a few
+ * rows of its output (pre-training: the labelled and the [CLS] rows, ~12 %; pooled-only heads: one row per sample).
+ *   rows[n_rows]: strictly ascending int64 indices into B*S, on the device; n_rows is the host's (0 <= n_rows <= B*S).
+ *   Contract: d_out is zero on every row that is not listed (listed rows may be zero too).  Nothing is detected from the data: a
+ *   gradient outside `rows` is silently dropped (vb_rows_check is the debug aid that looks).  Under that contract the entry computes
+ *   what vb_bert_layer_bwd computes: the two LayerNorm backwards (through the row map, the hidden-dropout mask replayed from the
+ *   ORIGINAL row number), the FFN-out / FFN-in / attention-out dgrads and their three weight gradients run on round_up(n_rows, 256)
+ *   compact rows (saved operands gathered, padding rows carry a zero gradient); dctx and dz1 are scattered back into zero-filled
+ *   [B*S, H] buffers and the attention backward, the QKV dgrad and the QKV weight gradient run on all rows as before.  Sums run over
+ *   fewer terms in another order, so results agree with the dense entry to rounding, not bit for bit.
+ *   VB_BF16 only: VB_ERR_UNSUPPORTED for the other dtypes (take the dense entry).  scratch: vb_bert_layer_bwd_rows_scratch_bytes(). */
+int64_t vb_bert_layer_bwd_rows_scratch_bytes(int dtype, int B, int S, int H, int I, int nh, int n_rows);
+int vb_bert_layer_bwd_rows(int dtype, const void* h_in, const void* h_out, const float* mask_add, const void* d_out, void* d_in,
+                           const void* saved, void* scratch, const void* const* weights, void* const* grads,
+                           const void* const* weights_t, const int64_t* ld_t,
+                           int B, int S, int H, int I, int nh, float p_hidden, float p_attn,
+                           uint64_t seed, uint32_t sid, const int64_t* rows, int n_rows, void* stream);
+/* debug aid of the contract above: bad[0] = 1 if x (T [M, H], H % 8 == 0) holds a non-zero on a row that `rows` does not list,
+ * bad[1] = 1 if `rows` is not strictly ascending within [0, M).  bad: two device ints (cleared here). */
+int vb_rows_check(int dtype, const void* x, const int64_t* rows, int n_rows, int M, int H, int* bad, void* stream);
 
 /* Optional per-stream timing of the GEMM launches (what bench.py's roofline object is measured with, over its timed region):
  * vb_stream_profile(stream, 1) makes every later vb_gemm / vb_wgrad_grouped launch ENQUEUED ON THAT STREAM record a HIP

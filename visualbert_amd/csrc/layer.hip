@@ -306,3 +306,164 @@ extern "C" int vb_bert_layer_bwd(int dtype, const void* h_in, const void* h_out,
     }
     return vb_reduce_jobs_launch(tail, stream);
 }
+
+// ---- the backward over the rows that carry a gradient ---------------------------------------------------------------------------
+// The LAST encoder layer of a model whose heads read a few rows of its output (the labelled and the [CLS] rows in pre-training: ~12 %;
+// one row per sample under a pooled-only head) receives a d_out that is zero on every other row.  Steps 1-5 of the backward above and
+// three of its four weight gradients act on one row at a time -- a zero row stays zero through all of them and adds exact zeros to
+// every column sum and weight gradient -- so they run here on the compact rows only; the attention backward mixes rows, and from there
+// on the layer is dense.
+namespace {
+
+constexpr int ROW_PAD = 256;          // compact row counts are rounded up to whole GEMM row tiles; padding rows carry a zero gradient
+
+// scratch of the row-map backward: the dense temporaries it still needs first, the compact ones behind them
+struct RowsScratch {
+    unsigned char *dctx, *dz1, *t_3h;                                   // dense [M, .]: contiguous dctx | dz1 (cleared by one launch)
+    float *dsum, *ln_ws, *ln_ws1;
+    unsigned char *dz2_c, *dfo_c, *da_c, *dz1_c, *dao_c, *dctx_c, *aout_c, *ctx_c;      // compact [n_pad, H]
+    unsigned char *pre_c, *inter_c, *dpre_c;                            // compact [n_pad, I]
+    size_t total;
+};
+RowsScratch carve_rows_scratch(unsigned char* base, const Dims& d, long n_pad) {
+    RowsScratch s;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { unsigned char* p = base ? base + o : nullptr; o += al(bytes); return p; };
+    s.dctx = take((size_t)d.M * d.H * d.es);
+    s.dz1 = take((size_t)d.M * d.H * d.es);
+    s.t_3h = take((size_t)d.M * 3 * d.H * d.es);
+    s.dsum = (float*)take((size_t)vb_attn_bwd_ws_floats((int)d.B, (int)d.S, (int)d.nh) * 4);
+    s.ln_ws = (float*)take((size_t)vb_ln_bwd_ws_bytes((int)d.M, d.H));
+    s.ln_ws1 = (float*)take((size_t)vb_ln_bwd_ws_bytes((int)d.M, d.H));
+    const size_t ch = (size_t)n_pad * d.H * d.es, ci = (size_t)n_pad * d.I * d.es;
+    s.dz2_c = take(ch); s.dfo_c = take(ch); s.da_c = take(ch); s.dz1_c = take(ch); s.dao_c = take(ch); s.dctx_c = take(ch);
+    s.aout_c = take(ch); s.ctx_c = take(ch);
+    s.pre_c = take(ci); s.inter_c = take(ci); s.dpre_c = take(ci);
+    s.total = o;
+    return s;
+}
+inline long rows_pad(int n_rows) { return ((long)n_rows + ROW_PAD - 1) / ROW_PAD * ROW_PAD; }
+
+}  // namespace
+
+extern "C" int64_t vb_bert_layer_bwd_rows_scratch_bytes(int dtype, int B, int S, int H, int I, int nh, int n_rows) {
+    Dims d;
+    if (!fill_dims(d, dtype, B, S, H, I, nh) || n_rows < 0 || n_rows > d.M) return -1;
+    if (dtype != VB_BF16) return -1;
+    return (int64_t)carve_rows_scratch(nullptr, d, rows_pad(n_rows)).total;
+}
+
+// rows[n_rows]: ascending int64 indices into B * S, on the device; d_out must be zero on every other row (the caller's promise: nothing
+// here looks at the data).  Computes what vb_bert_layer_bwd computes from such a d_out.  bf16 only (VB_ERR_UNSUPPORTED otherwise: the
+// caller takes the dense entry).  scratch: vb_bert_layer_bwd_rows_scratch_bytes() bytes.
+extern "C" int vb_bert_layer_bwd_rows(int dtype, const void* h_in, const void* h_out, const float* mask_add, const void* d_out, void* d_in,
+                                      const void* saved, void* scratch, const void* const* weights, void* const* grads,
+                                      const void* const* weights_t, const int64_t* ld_t,
+                                      int B, int S, int H, int I, int nh, float p_hidden, float p_attn,
+                                      uint64_t seed, uint32_t sid, const int64_t* rows, int n_rows, void* stream) {
+    Dims d;
+    if (!fill_dims(d, dtype, B, S, H, I, nh) || !h_in || !mask_add || !d_out || !d_in || !saved || !scratch ||
+        !weights || !grads || n_rows < 0 || n_rows > d.M || (n_rows > 0 && !rows))
+        return VB_ERR_ARG;
+    if (H <= 768 && !h_out) return VB_ERR_ARG;
+    if (dtype != VB_BF16) return VB_ERR_UNSUPPORTED;
+    float* G[VB_LW_COUNT];
+    for (int i = 0; i < VB_LW_COUNT; ++i) { G[i] = (float*)grads[i]; if (!G[i]) return VB_ERR_ARG; }
+    hipStream_t hs = (hipStream_t)stream;
+    const int M = (int)d.M;
+    if (n_rows == 0) {                                      // d_out = 0: every gradient of the layer is an exact zero
+        if (hipMemsetAsync(d_in, 0, (size_t)M * H * d.es, hs) != hipSuccess) return VB_ERR_LAUNCH;
+        return VB_OK;
+    }
+    const int n_pad = (int)rows_pad(n_rows);
+    Saved sv = carve_saved((unsigned char*)saved, d, p_attn > 0.f);
+    RowsScratch sc = carve_rows_scratch((unsigned char*)scratch, d, n_pad);
+    const void* wqkv = weights[VB_LW_QKV_W];
+    const void* wo = weights[VB_LW_AO_W];
+    const float* g1 = (const float*)weights[VB_LW_LN1_G]; const float* b1 = (const float*)weights[VB_LW_LN1_B];
+    const void* wi = weights[VB_LW_FI_W];
+    const void* wo2 = weights[VB_LW_FO_W];
+    const float* g2 = (const float*)weights[VB_LW_LN2_G]; const float* b2 = (const float*)weights[VB_LW_LN2_B];
+    const bool rb = H <= 768;
+    const int* rb1 = rb ? sv.ln_flags : nullptr;
+    const int* rb2 = rb ? sv.ln_flags + 1 : nullptr;
+    // the dense entry's dgrad at m rows
+    auto dgrad = [&](int m, const void* dy, int n_out, const void* w, int which_t, int n_in, void* dx, const void* addend,
+                     int act, const void* aux, float* colsum) -> int {
+        const void* wt = weights_t ? weights_t[which_t] : nullptr;
+        if (wt)
+            return vb_gemm(dtype, dtype, VB_KCONTIG, VB_KCONTIG, dy, n_out, wt, ld_t[which_t], dx, n_in, m, n_in, n_out,
+                           1.f, nullptr, nullptr, addend, n_in, act, aux, nullptr, n_in, 0, colsum, stream);
+        return vb_gemm(dtype, dtype, VB_KCONTIG, VB_KSTRIDED, dy, n_out, w, n_in, dx, n_in, m, n_in, n_out, 1.f, nullptr,
+                       nullptr, addend, n_in, act, aux, nullptr, n_in, 0, colsum, stream);
+    };
+    // the LayerNorm backwards write rows [0, n_rows) of their compact outputs: the padding rows of what a GEMM reads are cleared
+    auto clear_pad = [&](unsigned char* p) -> int {
+        if (n_pad == n_rows) return VB_OK;
+        return hipMemsetAsync(p + (size_t)n_rows * H * d.es, 0, (size_t)(n_pad - n_rows) * H * d.es, hs) == hipSuccess ? VB_OK : VB_ERR_LAUNCH;
+    };
+    VbReduceJobs tail{};
+    struct DeferScope {
+        explicit DeferScope(VbReduceJobs* j) { vb_reduce_defer_slot() = VB_DEFER_REDUCE ? j : nullptr; }
+        ~DeferScope() { vb_reduce_defer_slot() = nullptr; }
+    } defer_scope(&tail);
+    const int hb = (int)(H * d.es), ib = (int)(I * d.es);
+    // 0. the saved rows the compact GEMMs read: GELU', and the x operands of the three compact weight gradients
+    {
+        VbRowJobs g{{sv.pre, sv.inter, sv.a_out, sv.ctx}, {sc.pre_c, sc.inter_c, sc.aout_c, sc.ctx_c}, {ib, ib, hb, hb}, 4};
+        VB_TRY(vb_rows_gather(g, rows, n_rows, n_pad, stream));
+    }
+    // 1. output LayerNorm backward: d_out, z2 / h_out and the statistics through the map, dz2 and dfo compact
+    unsigned char* dz2 = sc.dz2_c;
+    unsigned char* dfo = p_hidden > 0.f ? sc.dfo_c : dz2;
+    VB_TRY(vb_ln_bwd_map(d.edt, d_out, sv.z2, sv.mean2, sv.rstd2, g2, dz2, dfo, G[VB_LW_LN2_G], G[VB_LW_LN2_B], G[VB_LW_FO_B], n_rows, H,
+                         p_hidden, sid + 4, 0.f, 0, seed, sc.ln_ws, nullptr, 0, h_out, b2, rb2, rows, 1, stream));
+    VB_TRY(clear_pad(dz2));
+    if (dfo != dz2) VB_TRY(clear_pad(dfo));
+    // 2. dpre = (dfo Wo2) * gelu'(pre) + the FFN-in bias gradient, n_pad rows
+    VB_TRY(dgrad(n_pad, dfo, H, wo2, VB_LWT_FO, I, sc.dpre_c, nullptr, VB_ACT_MUL_AUX, sc.pre_c, G[VB_LW_FI_B]));
+    // 3. da = dpre Wi + dz2
+    VB_TRY(dgrad(n_pad, sc.dpre_c, I, wi, VB_LWT_FI, H, sc.da_c, dz2, VB_ACT_NONE, nullptr, nullptr));
+    // 4. attention-output LayerNorm backward: dy compact, z1 / a_out and the statistics through the map
+    unsigned char* dz1c = sc.dz1_c;
+    unsigned char* dao = p_hidden > 0.f ? sc.dao_c : dz1c;
+    VB_TRY(vb_ln_bwd_map(d.edt, sc.da_c, sv.z1, sv.mean1, sv.rstd1, g1, dz1c, dao, G[VB_LW_LN1_G], G[VB_LW_LN1_B], G[VB_LW_AO_B], n_rows, H,
+                         p_hidden, sid + 1, 0.f, 0, seed, sc.ln_ws1, nullptr, 0, sv.a_out, b1, rb1, rows, 0, stream));
+    VB_TRY(clear_pad(dao));
+    // 5. dctx = dao Wo
+    VB_TRY(dgrad(n_pad, dao, H, wo, VB_LWT_AO, H, sc.dctx_c, nullptr, VB_ACT_NONE, nullptr, nullptr));
+    // 6. back to all rows: dctx and dz1 are zero outside the map
+    VB_TRY(vb_zero(sc.dctx, (int64_t)((sc.dz1 - sc.dctx) + al((size_t)M * H * d.es)), stream));
+    {
+        VbRowJobs s2{{sc.dctx_c, dz1c}, {sc.dctx, sc.dz1}, {hb, hb}, 2};
+        VB_TRY(vb_rows_scatter(s2, rows, n_rows, stream));
+    }
+    // 7-9. dense, as in vb_bert_layer_bwd: attention backward, dh = dqkv Wqkv + dz1
+    VB_TRY(vb_attn_bwd_sp(d.dtype, sv.qkv, mask_add, sc.dctx, sv.lse, sv.keepbits, sc.dsum, sc.t_3h, sv.ctx, G[VB_LW_QKV_B], B, S, nh,
+                          64, p_attn, seed, sid, nullptr, 1, stream));
+    VB_TRY(dgrad(M, sc.t_3h, 3 * H, wqkv, VB_LWT_QKV, H, d_in, sc.dz1, VB_ACT_NONE, nullptr, nullptr));
+    // 10. weight gradients: FFN-out, FFN-in, attention-out over the compact rows (one launch), QKV over all rows
+    {
+        const void* dys[3] = {dfo, sc.dpre_c, dao};
+        const int64_t ld_dy[3] = {H, I, H};
+        const void* xs[3] = {sc.inter_c, sc.aout_c, sc.ctx_c};
+        const int64_t ld_x[3] = {I, H, H};
+        void* dws[3] = {G[VB_LW_FO_W], G[VB_LW_FI_W], G[VB_LW_AO_W]};
+        const int64_t ld_dw[3] = {I, H, H};
+        const int n_out[3] = {H, I, H};
+        const int n_in[3] = {I, H, H};
+        VB_TRY(vb_wgrad_grouped(dtype, 3, dys, ld_dy, xs, ld_x, dws, ld_dw, n_out, n_in, n_pad, 1.f, nullptr, stream));
+    }
+    {
+        const void* dys[1] = {sc.t_3h};
+        const int64_t ld_dy[1] = {3 * H};
+        const void* xs[1] = {h_in};
+        const int64_t ld_x[1] = {H};
+        void* dws[1] = {G[VB_LW_QKV_W]};
+        const int64_t ld_dw[1] = {H};
+        const int n_out[1] = {3 * H};
+        const int n_in[1] = {H};
+        VB_TRY(vb_wgrad_grouped(dtype, 1, dys, ld_dy, xs, ld_x, dws, ld_dw, n_out, n_in, M, 1.f, nullptr, stream));
+    }
+    return vb_reduce_jobs_launch(tail, stream);
+}

@@ -189,6 +189,10 @@ struct LnBwdArgs {
     float* partials;     // [gridDim.x][3][H] when the two-stage column reduction is used, else NULL
     bf16* dx_split; long ld_split;     // fp32 only: also write dx (= dz when no dropout) as a bf16 hi | lo image, or NULL
     const void* y; const float* beta; const int* rebuild;   // *rebuild != 0: x-hat = (y - beta) / gamma (the forward wrote no z)
+    // row map (the MAP instantiations only; NULL otherwise): the launch visits M COMPACT rows; compact row m stands for row rows[m] of
+    // the saved tensors (z / y, mean, rstd) -- and of dy when dy_mapped -- and writes row m of dz / dx.  The input-dropout replay is
+    // keyed by the ORIGINAL element offset rows[m] * H + column: the mask the forward drew for that row.
+    const int64_t* rows; int dy_mapped;
 };
 
 // reduce this block's per-lane column partials across its 8 half-waves through LDS ([8][H] floats, plain
@@ -264,7 +268,7 @@ VB_DEVICE float wave_sum64(float v) {
     v += __shfl_xor(v, 32);
     return v;
 }
-template <typename T, int NC2, int MINW, int RB = 0>
+template <typename T, int NC2, int MINW, int RB = 0, bool MAP = false>
 VB_KERNEL VB_LAUNCH_BOUNDS2(NT, MINW) ln_bwd_kernel(LnBwdArgs a) {
     VB_DYN_SMEM(smem);
     float* lds = (float*)smem;
@@ -280,17 +284,19 @@ VB_KERNEL VB_LAUNCH_BOUNDS2(NT, MINW) ln_bwd_kernel(LnBwdArgs a) {
     const bool rebuild = RB && *a.rebuild != 0;
     const T* xsrc = (const T*)(rebuild ? a.y : a.z);
     for (int row = blockIdx.x * WAVES_PER_BLOCK + wave; row < a.M; row += gridDim.x * WAVES_PER_BLOCK) {
-        const float mean = a.mean[row], rstd = a.rstd[row];
+        long srow = row, drow = row;                       // row of the saved tensors / of dy (the outputs' row is `row`)
+        if constexpr (MAP) { srow = (long)a.rows[row]; drow = a.dy_mapped ? srow : (long)row; }
+        const float mean = a.mean[srow], rstd = a.rstd[srow];
         float dy[NC2][8], xh[NC2][8];
 #pragma unroll
         for (int ci = 0; ci < NC2; ++ci) {
             const int col = (lane + 64 * ci) * 8;
-            load8(dy[ci], (const T*)a.dy + (long)row * H + (col < H ? col : 0));
+            load8(dy[ci], (const T*)a.dy + drow * H + (col < H ? col : 0));
         }
 #pragma unroll
         for (int ci = 0; ci < NC2; ++ci) {
             const int col = (lane + 64 * ci) * 8;
-            load8(xh[ci], xsrc + (long)row * H + (col < H ? col : 0));
+            load8(xh[ci], xsrc + srow * H + (col < H ? col : 0));
         }
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -300,7 +306,7 @@ VB_KERNEL VB_LAUNCH_BOUNDS2(NT, MINW) ln_bwd_kernel(LnBwdArgs a) {
             const bool ok = col < H;
             float gm[8];
             load8(gm, a.gamma + colc);
-            if (a.dout.p > 0.f) apply_dropout8(dy[ci], a.dout, (uint64_t)((long)row * H + colc) >> 3);
+            if (a.dout.p > 0.f) apply_dropout8(dy[ci], a.dout, (uint64_t)(srow * H + colc) >> 3);
             if constexpr (RB == 1) {
                 float bt[8];
                 load8(bt, a.beta + colc);
@@ -335,7 +341,7 @@ VB_KERNEL VB_LAUNCH_BOUNDS2(NT, MINW) ln_bwd_kernel(LnBwdArgs a) {
             for (int j = 0; j < 8; ++j) dz[j] = rstd * (dy[ci][j] - s1 - xh[ci][j] * s2);
             if (ok) store8((T*)a.dz + e, dz);
             if (a.dx) {
-                if (a.din.p > 0.f) apply_dropout8(dz, a.din, (uint64_t)((long)row * H + (ok ? col : 0)) >> 3);
+                if (a.din.p > 0.f) apply_dropout8(dz, a.din, (uint64_t)(srow * H + (ok ? col : 0)) >> 3);
                 if (a.dx != a.dz && ok) store8((T*)a.dx + e, dz);
             }
             if constexpr (sizeof(T) == 4) { if (a.dx_split && ok) store_split8(a.dx_split + (long)row * a.ld_split + col, a.ld_split / 2, dz); }
@@ -399,7 +405,7 @@ template <int W> VB_DEVICE void dropw(float (&v)[W], const DropSpec& d, uint64_t
 #pragma unroll
     for (int j = 0; j < W; ++j) v[j] = rand8_keep(r, j, d.thresh) ? v[j] * d.scale : 0.0f;
 }
-template <typename T, bool RB>
+template <typename T, bool RB, bool MAP = false>
 VB_KERNEL VB_LAUNCH_BOUNDS2(NT, 4) ln_bwd12_kernel(LnBwdArgs a) {
     VB_DYN_SMEM(smem);
     float* lds = (float*)smem;
@@ -418,10 +424,14 @@ VB_KERNEL VB_LAUNCH_BOUNDS2(NT, 4) ln_bwd12_kernel(LnBwdArgs a) {
     typedef std::integral_constant<int, 4> W4;
 
     for (int row = blockIdx.x * WAVES_PER_BLOCK + wave; row < a.M; row += gridDim.x * WAVES_PER_BLOCK) {
-        const float mean = a.mean[row], rstd = a.rstd[row];
-        const long rb = (long)row * H;
+        long srow = row;                                   // row of the saved tensors (the outputs' row is `row`)
+        if constexpr (MAP) srow = (long)a.rows[row];
+        const float mean = a.mean[srow], rstd = a.rstd[srow];
+        const long rb = srow * H;                          // saved tensors and the dropout generator: the original row
+        const long rbo = MAP ? (long)row * H : rb;         // outputs: the compact row under a map
+        const long rbd = MAP && !a.dy_mapped ? rbo : rb;   // dy: mapped like the saved tensors, or compact already
         float dyA[8], dyB[4], xhA[8], xhB[4];
-        loadw<8>(dyA, (const T*)a.dy + rb + colA); loadw<4>(dyB, (const T*)a.dy + rb + colBc);
+        loadw<8>(dyA, (const T*)a.dy + rbd + colA); loadw<4>(dyB, (const T*)a.dy + rbd + colBc);
         loadw<8>(xhA, xsrc + rb + colA); loadw<4>(xhB, xsrc + rb + colBc);
         float s1 = 0.f, s2 = 0.f;
         // gamma / beta through a base the compiler cannot fold into a loop-invariant 64-bit lane address: kept that way they cost
@@ -463,13 +473,13 @@ VB_KERNEL VB_LAUNCH_BOUNDS2(NT, 4) ln_bwd12_kernel(LnBwdArgs a) {
         s2 = wave_sum64(s2) * invH;
         auto phase2 = [&](auto wtag, float (&g)[decltype(wtag)::value], float (&xh)[decltype(wtag)::value], int col, bool ok, float* ax) {
             constexpr int W = decltype(wtag)::value;
-            const long e = rb + col;
+            const long e = rbo + col;
             float dz[W];
 #pragma unroll
             for (int j = 0; j < W; ++j) dz[j] = rstd * (g[j] - s1 - xh[j] * s2);
             if (ok) storew<W>((T*)a.dz + e, dz);
             if (a.dx) {
-                if (a.din.p > 0.f) dropw<W>(dz, a.din, (uint64_t)e);
+                if (a.din.p > 0.f) dropw<W>(dz, a.din, (uint64_t)(MAP ? rb + col : e));
                 if (a.dx != a.dz && ok) storew<W>((T*)a.dx + e, dz);
             }
             if constexpr (sizeof(T) == 4) {
@@ -749,6 +759,17 @@ int vb_ln_bwd_sp(int dtype, const void* dy, const void* z, const float* mean, co
                  int M, int H, float p_in, uint32_t stream_in, float p_out, uint32_t stream_out,
                  uint64_t seed, float* ws, void* dx_split, int64_t ld_split, const void* y, const float* beta, const int* rebuild,
                  void* stream) {
+    return vb_ln_bwd_map(dtype, dy, z, mean, rstd, gamma, dz, dx, dgamma, dbeta, dbias, M, H, p_in, stream_in, p_out, stream_out, seed,
+                         ws, dx_split, ld_split, y, beta, rebuild, nullptr, 0, stream);
+}
+
+// rows != NULL: the M rows of the launch are the compact rows of a row map (LnBwdArgs::rows) -- separate instantiations, so the
+// kernels of a launch without a map are exactly what they were
+int vb_ln_bwd_map(int dtype, const void* dy, const void* z, const float* mean, const float* rstd,
+                  const float* gamma, void* dz, void* dx, float* dgamma, float* dbeta, float* dbias,
+                  int M, int H, float p_in, uint32_t stream_in, float p_out, uint32_t stream_out,
+                  uint64_t seed, float* ws, void* dx_split, int64_t ld_split, const void* y, const float* beta, const int* rebuild,
+                  const int64_t* rows, int dy_mapped, void* stream) {
     if (!dy || !z || !mean || !rstd || !gamma || !dz || M <= 0 || bad_h(H)) return VB_ERR_ARG;
     if (rebuild && (!y || !beta || p_out > 0.f || H > 768)) return VB_ERR_ARG;
     if (dx_split && (dtype != VB_F32 || (ld_split % 16) || ld_split < 2 * H || (((uintptr_t)dx_split) & 15))) return VB_ERR_ARG;
@@ -757,7 +778,7 @@ int vb_ln_bwd_sp(int dtype, const void* dy, const void* z, const float* mean, co
     if (dx_split && !dx) dx = dz;
     else if (p_in > 0.f && (!dx || dx == dz)) return VB_ERR_ARG;   // dropped and un-dropped grads differ
     LnBwdArgs a{dy, z, mean, rstd, gamma, dz, dx, dgamma, dbeta, dbias, M, H, make_drop(p_in, seed, stream_in),
-                make_drop(p_out, seed, stream_out), ws, (bf16*)dx_split, (long)ld_split, y, beta, rebuild};
+                make_drop(p_out, seed, stream_out), ws, (bf16*)dx_split, (long)ld_split, y, beta, rebuild, rows, dy_mapped};
     dim3 grid(row_grid(M, ws ? 1024 : 256));
     hipStream_t s = (hipStream_t)stream;
     const size_t smem = (size_t)(H + (H >> 5) + 1) * WAVES_PER_BLOCK * 3 * sizeof(float);      // padded pitch: ln_bwd12_kernel
@@ -766,7 +787,16 @@ int vb_ln_bwd_sp(int dtype, const void* dy, const void* z, const float* mean, co
     // step, 191.8 us in the rebuild-capable form (profiles/r04_ln_rebuild.txt).  The generic kernel's rebuild-capable form exists for
     // H <= 512 only (one chunk per lane, 87 VGPRs); with two full chunks it spills (340 us) -- layer.hip does not ask for it there.
     const bool twelve = H > 512 && H <= 768;
-    if (dtype == VB_BF16 && rebuild) {
+    if (rows) {
+        if (dtype != VB_BF16 && dtype != VB_F32) return VB_ERR_ARG;
+        if (rebuild && !twelve && H > 512) return VB_ERR_UNSUPPORTED;
+        const bool b = dtype == VB_BF16;
+        if (twelve && rebuild) { if (b) VB_LAUNCH((ln_bwd12_kernel<bf16, true, true>), grid, dim3(NT), smem, s, a); else VB_LAUNCH((ln_bwd12_kernel<float, true, true>), grid, dim3(NT), smem, s, a); }
+        else if (twelve) { if (b) VB_LAUNCH((ln_bwd12_kernel<bf16, false, true>), grid, dim3(NT), smem, s, a); else VB_LAUNCH((ln_bwd12_kernel<float, false, true>), grid, dim3(NT), smem, s, a); }
+        else if (rebuild) { if (b) VB_LAUNCH((ln_bwd_kernel<bf16, 1, 4, 1, true>), grid, dim3(NT), smem, s, a); else VB_LAUNCH((ln_bwd_kernel<float, 1, 4, 1, true>), grid, dim3(NT), smem, s, a); }
+        else if (H <= 512) { if (b) VB_LAUNCH((ln_bwd_kernel<bf16, 1, 4, 0, true>), grid, dim3(NT), smem, s, a); else VB_LAUNCH((ln_bwd_kernel<float, 1, 4, 0, true>), grid, dim3(NT), smem, s, a); }
+        else { if (b) VB_LAUNCH((ln_bwd_kernel<bf16, 2, 4, 0, true>), grid, dim3(NT), smem, s, a); else VB_LAUNCH((ln_bwd_kernel<float, 2, 4, 0, true>), grid, dim3(NT), smem, s, a); }
+    } else if (dtype == VB_BF16 && rebuild) {
         if (twelve) VB_LAUNCH((ln_bwd12_kernel<bf16, true>), grid, dim3(NT), smem, s, a);
         else if (H <= 512) VB_LAUNCH((ln_bwd_kernel<bf16, 1, 4, 1>), grid, dim3(NT), smem, s, a);
         else return VB_ERR_UNSUPPORTED;

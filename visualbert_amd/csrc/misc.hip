@@ -144,7 +144,100 @@ VB_KERNEL VB_LAUNCH_BOUNDS(NT) zero_kernel(u32x4* p, long n16) {
     for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n16; i += stride) p[i] = u32x4{0u, 0u, 0u, 0u};
 }
 
+// Whole rows through a row map (vb_rt.h: VbRowJobs; the compact backward of the last encoder layer, layer.hip): a thread moves one
+// 16-byte lane, blockIdx.y picks the tensor.  gather: compact row m <- row rows[m] (padding rows m >= n_rows copy row rows[0]: any
+// valid row will do, their gradient is zero); scatter: row rows[m] <- compact row m.
+VB_KERNEL VB_LAUNCH_BOUNDS(NT) rows_gather_kernel(VbRowJobs jobs, const int64_t* rows, int n_rows, int n_pad) {
+    const int j = blockIdx.y;
+    const u32x4* src = (const u32x4*)jobs.src[j];
+    u32x4* dst = (u32x4*)jobs.dst[j];
+    const int n16 = jobs.row_bytes[j] >> 4;
+    const long total = (long)n_pad * n16;
+    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < total; i += (long)gridDim.x * NT) {
+        const long m = i / n16;
+        const int c = (int)(i - m * n16);
+        const long r = (long)rows[m < n_rows ? m : 0];
+        dst[i] = src[r * n16 + c];
+    }
+}
+VB_KERNEL VB_LAUNCH_BOUNDS(NT) rows_scatter_kernel(VbRowJobs jobs, const int64_t* rows, int n_rows) {
+    const int j = blockIdx.y;
+    const u32x4* src = (const u32x4*)jobs.src[j];
+    u32x4* dst = (u32x4*)jobs.dst[j];
+    const int n16 = jobs.row_bytes[j] >> 4;
+    const long total = (long)n_rows * n16;
+    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < total; i += (long)gridDim.x * NT) {
+        const long m = i / n16;
+        const int c = (int)(i - m * n16);
+        dst[(long)rows[m] * n16 + c] = src[i];
+    }
+}
+// debug aid of the row-map backward: bad[0] = 1 if a row of x outside `rows` holds a non-zero, bad[1] = 1 if `rows` is not a
+// strictly ascending list of indices into [0, M).  A thread per (row, 8-column chunk); membership by binary search.
+template <typename T>
+VB_KERNEL VB_LAUNCH_BOUNDS(NT) rows_check_kernel(const T* x, const int64_t* rows, int n_rows, int M, int H, int* bad) {
+    const int chunks = H / 8;
+    const long total = (long)M * chunks;
+    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < total; i += (long)gridDim.x * NT) {
+        const long r = i / chunks;
+        int lo = 0, hi = n_rows;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if ((long)rows[mid] < r) lo = mid + 1; else hi = mid;
+        }
+        if (lo < n_rows && (long)rows[lo] == r) continue;
+        float v[8];
+        load8(v, x + i * 8);
+        bool nz = false;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) nz |= !(v[e] == 0.0f);
+        if (nz) bad[0] = 1;
+    }
+    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n_rows; i += (long)gridDim.x * NT) {
+        const long r = (long)rows[i];
+        if (r < 0 || r >= M || (i > 0 && (long)rows[i - 1] >= r)) bad[1] = 1;
+    }
+}
+
 }  // namespace
+
+static inline unsigned rows_grid(long lanes) {
+    long b = (lanes + NT - 1) / NT;
+    return (unsigned)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
+}
+static bool rows_jobs_ok(const VbRowJobs& jobs) {
+    if (jobs.n < 1 || jobs.n > 4) return false;
+    for (int j = 0; j < jobs.n; ++j)
+        if (!jobs.src[j] || !jobs.dst[j] || jobs.row_bytes[j] <= 0 || (jobs.row_bytes[j] & 15) ||
+            ((((uintptr_t)jobs.src[j]) | ((uintptr_t)jobs.dst[j])) & 15))
+            return false;
+    return true;
+}
+int vb_rows_gather(const VbRowJobs& jobs, const int64_t* rows, int n_rows, int n_pad, void* stream) {
+    if (!rows || n_rows < 1 || n_pad < n_rows || !rows_jobs_ok(jobs)) return VB_ERR_ARG;
+    int widest = 0;
+    for (int j = 0; j < jobs.n; ++j) widest = jobs.row_bytes[j] > widest ? jobs.row_bytes[j] : widest;
+    VB_LAUNCH(rows_gather_kernel, dim3(rows_grid((long)n_pad * (widest >> 4)), (unsigned)jobs.n), dim3(NT), 0, (hipStream_t)stream, jobs, rows,
+              n_rows, n_pad);
+    return vb_check_launch();
+}
+int vb_rows_scatter(const VbRowJobs& jobs, const int64_t* rows, int n_rows, void* stream) {
+    if (!rows || n_rows < 1 || !rows_jobs_ok(jobs)) return VB_ERR_ARG;
+    int widest = 0;
+    for (int j = 0; j < jobs.n; ++j) widest = jobs.row_bytes[j] > widest ? jobs.row_bytes[j] : widest;
+    VB_LAUNCH(rows_scatter_kernel, dim3(rows_grid((long)n_rows * (widest >> 4)), (unsigned)jobs.n), dim3(NT), 0, (hipStream_t)stream, jobs, rows,
+              n_rows);
+    return vb_check_launch();
+}
+extern "C" int vb_rows_check(int dtype, const void* x, const int64_t* rows, int n_rows, int M, int H, int* bad, void* stream) {
+    if (!x || !bad || n_rows < 0 || (n_rows > 0 && !rows) || M <= 0 || H <= 0 || (H % 8) || (((uintptr_t)x) & 15)) return VB_ERR_ARG;
+    if (hipMemsetAsync(bad, 0, 2 * sizeof(int), (hipStream_t)stream) != hipSuccess) return VB_ERR_LAUNCH;
+    const dim3 grid(rows_grid((long)M * (H / 8)));
+    if (dtype == VB_BF16) VB_LAUNCH(rows_check_kernel<bf16>, grid, dim3(NT), 0, (hipStream_t)stream, (const bf16*)x, rows, n_rows, M, H, bad);
+    else if (dtype == VB_F32) VB_LAUNCH(rows_check_kernel<float>, grid, dim3(NT), 0, (hipStream_t)stream, (const float*)x, rows, n_rows, M, H, bad);
+    else return VB_ERR_ARG;
+    return vb_check_launch();
+}
 
 extern "C" const char* vb_version(void) {
 #ifdef VB_EMU

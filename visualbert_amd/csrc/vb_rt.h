@@ -700,6 +700,19 @@ __attribute__((visibility("hidden"))) int vb_ln_bwd_sp(int dtype, const void* dy
     const float* gamma, void* dz, void* dx, float* dgamma, float* dbeta, float* dbias, int M, int H, float p_in, uint32_t stream_in,
     float p_out, uint32_t stream_out, uint64_t seed, float* ws, void* dx_split, int64_t ld_split, const void* y, const float* beta,
     const int* rebuild, void* stream);
+// vb_ln_bwd_sp over a row map (layer.hip: vb_bert_layer_bwd_rows): the launch's M rows are compact rows; rows[m] (ascending int64, device)
+// is the row of z / y / mean / rstd -- and of dy when dy_mapped -- that compact row m stands for, and the row whose input-dropout mask is
+// replayed; dz / dx (and the image) are written compact.  rows == NULL: vb_ln_bwd_sp.
+__attribute__((visibility("hidden"))) int vb_ln_bwd_map(int dtype, const void* dy, const void* z, const float* mean, const float* rstd,
+    const float* gamma, void* dz, void* dx, float* dgamma, float* dbeta, float* dbias, int M, int H, float p_in, uint32_t stream_in,
+    float p_out, uint32_t stream_out, uint64_t seed, float* ws, void* dx_split, int64_t ld_split, const void* y, const float* beta,
+    const int* rebuild, const int64_t* rows, int dy_mapped, void* stream);
+// whole-row gather / scatter through a row map (misc.hip), up to four tensors per launch: 16-byte lanes, row_bytes[j] % 16 == 0.
+//   gather : dst[j][m, :] = src[j][rows[m], :] for m < n_rows; the padding rows n_rows <= m < n_pad copy row rows[0] (any valid row)
+//   scatter: dst[j][rows[m], :] = src[j][m, :] for m < n_rows (dst is NOT cleared here)
+struct VbRowJobs { const void* src[4]; void* dst[4]; int row_bytes[4]; int n; };
+__attribute__((visibility("hidden"))) int vb_rows_gather(const VbRowJobs& jobs, const int64_t* rows, int n_rows, int n_pad, void* stream);
+__attribute__((visibility("hidden"))) int vb_rows_scatter(const VbRowJobs& jobs, const int64_t* rows, int n_rows, void* stream);
 __attribute__((visibility("hidden"))) int vb_attn_fwd_sp(int dtype, const void* qkv, const float* mask_add, void* ctx, float* lse,
     uint64_t* keepbits, int B, int S, int nh, int head_dim, float p_drop, uint64_t seed, uint32_t stream_id, void* ctx_split,
     int split_only, void* stream);

@@ -1128,10 +1128,11 @@ class TrainVisualBERTObjective(PreTrainedBertModel):
                 flat_masked_lm_labels = ext
         else:
             flat_attention_mask = flat_input_mask
+        row_plan = None
         if self.training_head_type in ("pretraining", "vqa_advanced") and flat_masked_lm_labels is not None \
                 and not output_all_encoded_layers:
             flat_masked_lm_labels = flat_masked_lm_labels.contiguous()
-            ops.plan_masked_rows(flat_masked_lm_labels)      # count the labelled rows now, read the count 12 layers later
+            row_plan = ops.plan_masked_rows(flat_masked_lm_labels)      # count the labelled rows now, read the count 12 layers later
 
         if self.output_attention_weights:                    # modeling.py:1428-1442
             _, _, attention_weights = self.bert(
@@ -1147,6 +1148,10 @@ class TrainVisualBERTObjective(PreTrainedBertModel):
             image_text_alignment=flat_image_text_alignment, confidence=None,
             output_all_encoded_layers=output_all_encoded_layers)
 
+        # The heads below are the ONLY consumers of sequence_output (it is not returned), so where a head reads a known set of its
+        # rows, the gradient of the last encoder layer's output is zero on every other row and the layer is told so
+        # (ops.offer_grad_rows: the row-wise part of its backward then runs on those rows only).  Every other configuration --
+        # all encoded layers returned, attention weights, the alignment / flickr heads, the sparse MLM head, fp32 / bf16x3 -- stays dense.
         output_dict = {}
         if output_all_encoded_layers:
             output_dict["sequence_output"] = sequence_output
@@ -1168,6 +1173,8 @@ class TrainVisualBERTObjective(PreTrainedBertModel):
                 logits, mlm_loss = ops.MLMHeadLossFn.apply(
                     sequence_output, flat_masked_lm_labels, pred, pred.decoder.weight, pred.bias, tr.dense.weight,
                     tr.dense.bias, tr.LayerNorm.weight, tr.LayerNorm.bias)
+                if row_plan is not None:                     # MLM head: the labelled rows; pooler: the [CLS] row of every sample
+                    ops.offer_grad_rows(sequence_output, row_plan.rows_with_first())
             rel, nsp_loss = ops.SmallLinearCEFn.apply(pooled_output, is_random_next, -1,
                                                       self.cls.seq_relationship.weight, self.cls.seq_relationship.bias)
             output_dict["logits"] = logits
@@ -1223,9 +1230,15 @@ class TrainVisualBERTObjective(PreTrainedBertModel):
             return output_dict
 
         if self.training_head_type == "vqa":
-            logits, loss, acc, _ = ops.VQAHeadLossFn.apply(
+            logits, loss, acc, vqa_idx = ops.VQAHeadLossFn.apply(
                 sequence_output, flat_input_mask, label, _drop_p(self.dropout, self.training), 9,
                 self.classifier.weight, self.classifier.bias)
+            if label is not None and ops.grad_rows_enabled():
+                # the head read ONE gathered row per sample (the pooled output is not used): index input_mask.sum(1) - 2, wrapped /
+                # clamped as the gather kernel does
+                Bq, Sq = sequence_output.shape[:2]
+                pos = torch.where(vqa_idx < 0, vqa_idx + Sq, vqa_idx).clamp_(0, Sq - 1)
+                ops.offer_grad_rows(sequence_output, ops.first_token_rows(Bq, Sq, sequence_output.device) + pos)
             output_dict["logits"] = logits
             output_dict["loss"] = None
             output_dict["accuracy"] = None
@@ -1240,6 +1253,9 @@ class TrainVisualBERTObjective(PreTrainedBertModel):
             if p > 0.0:
                 po = _small_dropout(po, p)
             logits, loss = ops.SmallLinearCEFn.apply(po, label, -100, self.classifier.weight, self.classifier.bias)
+            if label is not None:                            # pooled-only head: the [CLS] row of every sample
+                ops.offer_grad_rows(sequence_output, ops.first_token_rows(sequence_output.size(0), sequence_output.size(1),
+                                                                          sequence_output.device))
             output_dict["logits"] = logits
             output_dict["loss"] = loss if label is not None else None
             return output_dict

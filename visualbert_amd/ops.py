@@ -15,6 +15,7 @@ Conventions
     otherwise a fresh fp32 gradient is returned to autograd as usual.
   * dropout masks are regenerated in backward from (seed, stream id); forward draws the seed.
 """
+import os
 import threading
 
 import torch
@@ -560,12 +561,33 @@ class MaskedRowPlan:
         self.valid = lab != -1
         self.count_host = None
         self.event = None
+        # [B, S] labels: also the labelled rows UNITED with the first row of every sample -- the rows of the last encoder layer's
+        # output that the pre-training heads read (MLM head: labelled rows; pooler: [CLS]).  Counted from the data, not assumed
+        # disjoint: a caller may label position 0.
+        self.valid_first = None
+        if labels.dim() == 2 and grad_rows_enabled() and torch.is_grad_enabled():
+            self.valid_first = self.valid.clone()
+            self.valid_first.view(labels.shape)[:, 0] = True
         if lab.is_cuda:
-            cnt = self.valid.sum(dtype=torch.int64)
-            self.count_host = torch.empty(1, dtype=torch.int64, pin_memory=True)
+            cnt = self.valid.sum(dtype=torch.int64).reshape(1)
+            if self.valid_first is not None:
+                cnt = torch.cat((cnt, self.valid_first.sum(dtype=torch.int64).reshape(1)))
+            self.count_host = torch.empty(cnt.numel(), dtype=torch.int64, pin_memory=True)
             self.count_host.copy_(cnt, non_blocking=True)
             self.event = torch.cuda.Event()
             self.event.record()
+
+    def rows_with_first(self):
+        """int64 indices (ascending) of the labelled rows and the first row of every sample, or None without [B, S] labels."""
+        if self.valid_first is None:
+            return None
+        if self.event is None:
+            return torch.nonzero(self.valid_first).reshape(-1)
+        self.event.synchronize()
+        try:
+            return torch.nonzero_static(self.valid_first, size=int(self.count_host[1])).reshape(-1)   # sized on the host: no sync
+        except (RuntimeError, NotImplementedError):
+            return torch.nonzero(self.valid_first).reshape(-1)
 
     def rows(self):
         """int64 indices of the labelled rows (ascending)."""
@@ -583,11 +605,104 @@ class MaskedRowPlan:
 
 _row_plan = None
 
+# ------------------------------------------------------------------------------------------------
+# rows of the LAST encoder layer's output that carry a gradient.  A model that built every consumer of that output itself knows
+# which rows its heads read (modeling.TrainVisualBERTObjective: labelled + [CLS] rows in pre-training, one row per sample under a
+# pooled-only head); it hands the list to the layer's autograd node and the layer's backward runs its row-wise part on those
+# rows only (vb_bert_layer_bwd_rows).  Nothing is detected from the data; a layer that was handed nothing runs dense.
+# VB_GRAD_ROWS=0 / set_grad_rows(False): always dense (A/B runs, tests).
+# VB_GRAD_ROWS_CHECK=1 / set_grad_rows_check(True): debug -- verify on the device that the gradient IS zero outside the rows
+# (one host sync per step) and raise if not.
+# ------------------------------------------------------------------------------------------------
+_grad_rows = {"on": os.environ.get("VB_GRAD_ROWS", "1") != "0", "check": os.environ.get("VB_GRAD_ROWS_CHECK", "0") == "1",
+              "taken": 0}
+
+
+def set_grad_rows(on):
+    old = _grad_rows["on"]
+    _grad_rows["on"] = bool(on)
+    return old
+
+
+def grad_rows_enabled():
+    return _grad_rows["on"]
+
+
+def set_grad_rows_check(on):
+    old = _grad_rows["check"]
+    _grad_rows["check"] = bool(on)
+    return old
+
+
+def grad_rows_taken():
+    """how many layer backwards took the rows entry so far (tests, A/B scripts)."""
+    return _grad_rows["taken"]
+
+
+def offer_grad_rows(seq, rows):
+    """`seq` is the output of a BertLayerFn and every gradient that will reach it is zero outside `rows` (ascending int64
+    indices into B*S, on seq's device): the caller's promise.  Returns whether the layer took the offer."""
+    if rows is None or not _grad_rows["on"] or not torch.is_grad_enabled():
+        return False
+    fn = seq.grad_fn
+    if fn is None or type(fn).__name__ != "BertLayerFnBackward" or seq.dtype != torch.bfloat16 or _x3[0]:
+        return False
+    if rows.dtype != torch.int64 or rows.device != seq.device:
+        raise RuntimeError("visualbert_amd: offer_grad_rows needs int64 row indices on %s" % (seq.device,))
+    fn._vb_grad_rows = rows.contiguous()
+    return True
+
+
+_first_rows = {}
+
+
+def first_token_rows(B, S, device):
+    """b * S for every sample b: the rows a pooled-only head reads (cached per shape)."""
+    key = (B, S, device)
+    r = _first_rows.get(key)
+    if r is None:
+        if len(_first_rows) > 8:
+            _first_rows.clear()
+        r = _first_rows[key] = torch.arange(B, dtype=torch.int64, device=device) * S
+    return r
+
+
+def _layer_bwd_call(L, rows, code, h2, out, mask_add, dy2, d_in, saved, w_arr, g_arr, wt_arr, ld_arr, cfg):
+    """vb_bert_layer_bwd, or vb_bert_layer_bwd_rows when the layer was handed its gradient's rows (dense again when the entry
+    declines: VB_ERR_UNSUPPORTED)."""
+    B, S, H, I, nh, p_hidden, p_attn, seed, sid = cfg
+    dense = _layer_bytes(L, code, B, S, H, I, nh, p_attn)[1]
+    if rows is not None and _grad_rows["on"] and code == _lib.VB_BF16:
+        n = int(rows.numel())
+        if _grad_rows["check"]:
+            bad = torch.empty(2, dtype=torch.int32, device=dy2.device)
+            check(L.vb_rows_check(code, ptr(dy2), ptr(rows) if n else None, n, B * S, H, ptr(bad), stream_ptr()), "vb_rows_check")
+            b0, b1 = bad.tolist()
+            if b0 or b1:
+                raise RuntimeError("visualbert_amd: the gradient of the last encoder layer's output %s (VB_GRAD_ROWS_CHECK)" % (
+                    "is not zero outside the rows its consumers declared" if b0 else "came with a row list that is not ascending"))
+        nscr = L.vb_bert_layer_bwd_rows_scratch_bytes(code, B, S, H, I, nh, n)
+        if nscr >= 0:
+            scratch = layer_scratch(max(nscr, dense), h2.device)
+            rc = L.vb_bert_layer_bwd_rows(code, ptr(h2), ptr(out), ptr(mask_add), ptr(dy2), ptr(d_in), ptr(saved), ptr(scratch),
+                                          w_arr, g_arr, wt_arr, ld_arr, B, S, H, I, nh, float(p_hidden), float(p_attn), seed, sid,
+                                          ptr(rows) if n else None, n, stream_ptr())
+            if rc == 0:
+                _grad_rows["taken"] += 1
+                return
+            if rc != -3:                                       # VB_ERR_UNSUPPORTED: nothing was launched, run dense
+                check(rc, "vb_bert_layer_bwd_rows")
+    scratch = layer_scratch(dense, h2.device)
+    check(L.vb_bert_layer_bwd(code, ptr(h2), ptr(out), ptr(mask_add), ptr(dy2), ptr(d_in), ptr(saved), ptr(scratch),
+                              w_arr, g_arr, wt_arr, ld_arr, B, S, H, I, nh,
+                              float(p_hidden), float(p_attn), seed, sid, stream_ptr()), "vb_bert_layer_bwd")
+
 
 def plan_masked_rows(labels):
     """call as early as the (extended) MLM labels exist; MLMHeadLossFn picks the plan up by tensor identity."""
     global _row_plan
     _row_plan = MaskedRowPlan(labels) if labels is not None else None
+    return _row_plan
 
 
 def _rows_for(lab):
@@ -1080,14 +1195,13 @@ class BertLayerFn(torch.autograd.Function):
         if not dy2.is_contiguous():
             dy2 = dy2.contiguous()
         L = _lib.lib()
-        scratch = layer_scratch(_layer_bytes(L, code, B, S, H, I, nh, p_attn)[1], h2.device)
+        rows = getattr(ctx, "_vb_grad_rows", None)           # offer_grad_rows: the last layer of a model that knows its heads
         plan = _layer_plan(layer, pc, dt)
         if plan is not None:
             d_in = torch.empty((B * S, H), dtype=dt, device=h2.device)
             plan.arena.touched.update(plan.touched)          # "this step wrote a gradient for these parameters" (grad_target's bookkeeping)
-            check(L.vb_bert_layer_bwd(code, ptr(h2), ptr(out), ptr(mask_add), ptr(dy2), ptr(d_in), ptr(saved), ptr(scratch),
-                                      plan.w_arr, plan.g_arr, plan.wt_arr, plan.ld_arr, B, S, H, I, nh,
-                                      float(p_hidden), float(p_attn), seed, sid, stream_ptr()), "vb_bert_layer_bwd")
+            _layer_bwd_call(L, rows, code, h2, out, mask_add, dy2, d_in, saved, plan.w_arr, plan.g_arr, plan.wt_arr, plan.ld_arr,
+                            ctx.cfg)
             return (d_in.view(B, S, H), None, None, None, None) + _NONE16
         weights = [weight_for(sa.qkv_weight, dt), sa.qkv_bias, weight_for(so.dense.weight, dt), so.dense.bias.detach(),
                    so.LayerNorm.weight.detach(), so.LayerNorm.bias.detach(),
@@ -1110,9 +1224,8 @@ class BertLayerFn(torch.autograd.Function):
                 w_ = w_.buf
             wt_arr[i] = w_.data_ptr() if w_ is not None else None
             ld_arr[i] = w_.stride(0) if w_ is not None else 0
-        check(L.vb_bert_layer_bwd(code, ptr(h2), ptr(out), ptr(mask_add), ptr(dy2), ptr(d_in), ptr(saved), ptr(scratch),
-                                  _ptr_array(weights), _ptr_array(grads), wt_arr, ld_arr, B, S, H, I, nh,
-                                  float(p_hidden), float(p_attn), seed, sid, stream_ptr()), "vb_bert_layer_bwd")
+        _layer_bwd_call(L, rows, code, h2, out, mask_add, dy2, d_in, saved, _ptr_array(weights), _ptr_array(grads), wt_arr, ld_arr,
+                        ctx.cfg)
         if direct_qkv:
             gq = [None] * 6
         else:
