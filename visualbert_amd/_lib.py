@@ -104,8 +104,9 @@ class StreamOpts(ctypes.Structure):
     """include/visualbert_hip.h: vb_stream_opts"""
     _fields_ = [("persistent_workgroups", _i), ("nt_kernel", _i), ("attn_two_pass", _i), ("reserved", _i)]
 
-_ERRORS = {-1: "VB_ERR_ARG (bad argument)", -2: "VB_ERR_LAUNCH (hip launch failed)",
-           -3: "VB_ERR_UNSUPPORTED (shape/dtype not supported by this kernel)"}
+VB_OK, VB_ERR_ARG, VB_ERR_LAUNCH, VB_ERR_UNSUPPORTED = 0, -1, -2, -3      # include/visualbert_hip.h
+_ERRORS = {VB_ERR_ARG: "VB_ERR_ARG (bad argument)", VB_ERR_LAUNCH: "VB_ERR_LAUNCH (hip launch failed)",
+           VB_ERR_UNSUPPORTED: "VB_ERR_UNSUPPORTED (shape/dtype not supported by this kernel)"}
 
 _lib = None
 _lib_path = None

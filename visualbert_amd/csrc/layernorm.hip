@@ -707,6 +707,25 @@ static inline unsigned row_grid(long rows, int cap) {
     return (unsigned)g;
 }
 
+// The LayerNorm backward's kernel form: (element type, form, rebuild-capable, rows through a map).  Every combination is its own
+// instantiation -- a launch without a map / without the rebuild runs exactly the kernel it ran before those existed -- except the
+// two-chunk form with the rebuild, which does not exist (vb_ln_bwd_map: the choice of the form)
+enum LnBwdForm { LN_BWD_TWELVE, LN_BWD_ONE_CHUNK, LN_BWD_TWO_CHUNK };
+
+template <typename T, bool RB, bool MAP>
+int ln_bwd_launch(LnBwdForm form, dim3 grid, size_t smem, hipStream_t s, const LnBwdArgs& a) {
+    if (form == LN_BWD_TWELVE) VB_LAUNCH((ln_bwd12_kernel<T, RB, MAP>), grid, dim3(NT), smem, s, a);
+    else if (form == LN_BWD_ONE_CHUNK) VB_LAUNCH((ln_bwd_kernel<T, 1, 4, RB, MAP>), grid, dim3(NT), smem, s, a);
+    else if constexpr (RB) return VB_ERR_UNSUPPORTED;
+    else VB_LAUNCH((ln_bwd_kernel<T, 2, 4, 0, MAP>), grid, dim3(NT), smem, s, a);
+    return VB_OK;
+}
+template <typename T>
+int ln_bwd_select(LnBwdForm form, bool rb, bool map, dim3 grid, size_t smem, hipStream_t s, const LnBwdArgs& a) {
+    if (rb) return map ? ln_bwd_launch<T, true, true>(form, grid, smem, s, a) : ln_bwd_launch<T, true, false>(form, grid, smem, s, a);
+    return map ? ln_bwd_launch<T, false, true>(form, grid, smem, s, a) : ln_bwd_launch<T, false, false>(form, grid, smem, s, a);
+}
+
 }  // namespace
 
 extern "C" int vb_ln_fwd(int dtype, const void* x, const void* resid, void* z_out, void* y, float* mean, float* rstd,
@@ -786,33 +805,11 @@ int vb_ln_bwd_map(int dtype, const void* dy, const void* z, const float* mean, c
     // 512 < H <= 768: twelve columns per lane (113 VGPRs, no spills, every lane busy): 188.7 -> 182.4 us per launch at M = 167,936 in the
     // step, 191.8 us in the rebuild-capable form (profiles/r04_ln_rebuild.txt).  The generic kernel's rebuild-capable form exists for
     // H <= 512 only (one chunk per lane, 87 VGPRs); with two full chunks it spills (340 us) -- layer.hip does not ask for it there.
-    const bool twelve = H > 512 && H <= 768;
-    if (rows) {
-        if (dtype != VB_BF16 && dtype != VB_F32) return VB_ERR_ARG;
-        if (rebuild && !twelve && H > 512) return VB_ERR_UNSUPPORTED;
-        const bool b = dtype == VB_BF16;
-        if (twelve && rebuild) { if (b) VB_LAUNCH((ln_bwd12_kernel<bf16, true, true>), grid, dim3(NT), smem, s, a); else VB_LAUNCH((ln_bwd12_kernel<float, true, true>), grid, dim3(NT), smem, s, a); }
-        else if (twelve) { if (b) VB_LAUNCH((ln_bwd12_kernel<bf16, false, true>), grid, dim3(NT), smem, s, a); else VB_LAUNCH((ln_bwd12_kernel<float, false, true>), grid, dim3(NT), smem, s, a); }
-        else if (rebuild) { if (b) VB_LAUNCH((ln_bwd_kernel<bf16, 1, 4, 1, true>), grid, dim3(NT), smem, s, a); else VB_LAUNCH((ln_bwd_kernel<float, 1, 4, 1, true>), grid, dim3(NT), smem, s, a); }
-        else if (H <= 512) { if (b) VB_LAUNCH((ln_bwd_kernel<bf16, 1, 4, 0, true>), grid, dim3(NT), smem, s, a); else VB_LAUNCH((ln_bwd_kernel<float, 1, 4, 0, true>), grid, dim3(NT), smem, s, a); }
-        else { if (b) VB_LAUNCH((ln_bwd_kernel<bf16, 2, 4, 0, true>), grid, dim3(NT), smem, s, a); else VB_LAUNCH((ln_bwd_kernel<float, 2, 4, 0, true>), grid, dim3(NT), smem, s, a); }
-    } else if (dtype == VB_BF16 && rebuild) {
-        if (twelve) VB_LAUNCH((ln_bwd12_kernel<bf16, true>), grid, dim3(NT), smem, s, a);
-        else if (H <= 512) VB_LAUNCH((ln_bwd_kernel<bf16, 1, 4, 1>), grid, dim3(NT), smem, s, a);
-        else return VB_ERR_UNSUPPORTED;
-    } else if (dtype == VB_BF16) {
-        if (twelve) VB_LAUNCH((ln_bwd12_kernel<bf16, false>), grid, dim3(NT), smem, s, a);
-        else if (H <= 512) VB_LAUNCH((ln_bwd_kernel<bf16, 1, 4>), grid, dim3(NT), smem, s, a);
-        else VB_LAUNCH((ln_bwd_kernel<bf16, 2, 4>), grid, dim3(NT), smem, s, a);
-    } else if (dtype == VB_F32 && rebuild) {
-        if (twelve) VB_LAUNCH((ln_bwd12_kernel<float, true>), grid, dim3(NT), smem, s, a);
-        else if (H <= 512) VB_LAUNCH((ln_bwd_kernel<float, 1, 4, 1>), grid, dim3(NT), smem, s, a);
-        else return VB_ERR_UNSUPPORTED;
-    } else if (dtype == VB_F32) {
-        if (twelve) VB_LAUNCH((ln_bwd12_kernel<float, false>), grid, dim3(NT), smem, s, a);
-        else if (H <= 512) VB_LAUNCH((ln_bwd_kernel<float, 1, 4>), grid, dim3(NT), smem, s, a);
-        else VB_LAUNCH((ln_bwd_kernel<float, 2, 4>), grid, dim3(NT), smem, s, a);
-    } else return VB_ERR_ARG;
+    const LnBwdForm form = H > 512 && H <= 768 ? LN_BWD_TWELVE : (H <= 512 ? LN_BWD_ONE_CHUNK : LN_BWD_TWO_CHUNK);
+    if (dtype != VB_BF16 && dtype != VB_F32) return VB_ERR_ARG;
+    const int rc = dtype == VB_BF16 ? ln_bwd_select<bf16>(form, rebuild != nullptr, rows != nullptr, grid, smem, s, a)
+                                    : ln_bwd_select<float>(form, rebuild != nullptr, rows != nullptr, grid, smem, s, a);
+    if (rc != VB_OK) return rc;
     if (ws && (dgamma || dbeta || dbias)) {
         const int slices = grid.x >= 256 ? 4 : 1;
         VbReduceJobs* defer = vb_reduce_defer_slot();

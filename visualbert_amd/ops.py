@@ -687,10 +687,10 @@ def _layer_bwd_call(L, rows, code, h2, out, mask_add, dy2, d_in, saved, w_arr, g
             rc = L.vb_bert_layer_bwd_rows(code, ptr(h2), ptr(out), ptr(mask_add), ptr(dy2), ptr(d_in), ptr(saved), ptr(scratch),
                                           w_arr, g_arr, wt_arr, ld_arr, B, S, H, I, nh, float(p_hidden), float(p_attn), seed, sid,
                                           ptr(rows) if n else None, n, stream_ptr())
-            if rc == 0:
+            if rc == _lib.VB_OK:
                 _grad_rows["taken"] += 1
                 return
-            if rc != -3:                                       # VB_ERR_UNSUPPORTED: nothing was launched, run dense
+            if rc != _lib.VB_ERR_UNSUPPORTED:                  # (declined: nothing was launched, run dense)
                 check(rc, "vb_bert_layer_bwd_rows")
     scratch = layer_scratch(dense, h2.device)
     check(L.vb_bert_layer_bwd(code, ptr(h2), ptr(out), ptr(mask_add), ptr(dy2), ptr(d_in), ptr(saved), ptr(scratch),
@@ -1078,6 +1078,34 @@ def layer_params(layer):
     return c
 
 
+def _layer_weights(pc, dt):
+    """the 12 forward operands of a layer (pc: layer_params(layer)) in VB_LW_* order: matrices in dt, biases / LayerNorm fp32.
+    (weight_for refreshes a stale shadow as a side effect)"""
+    (at, sa, so, im, om), _, _ = pc
+    return [weight_for(sa.qkv_weight, dt), sa.qkv_bias, weight_for(so.dense.weight, dt), so.dense.bias.detach(),
+            so.LayerNorm.weight.detach(), so.LayerNorm.bias.detach(),
+            weight_for(im.dense.weight, dt), im.dense.bias.detach(),
+            weight_for(om.dense.weight, dt), om.dense.bias.detach(),
+            om.LayerNorm.weight.detach(), om.LayerNorm.bias.detach()]
+
+
+def _layer_weights_t(pc, dt):
+    """(the four transposed weights in VB_LWT_* order, their pointer array, their leading-dimension array); an entry may be None
+    (no shadow: NULL, the library reads the weight K-strided) or a SplitOperand (bf16x3: its buffer)"""
+    import ctypes
+    (at, sa, so, im, om), _, _ = pc
+    wts = [weight_t_for(sa.qkv_weight, dt), weight_t_for(so.dense.weight, dt), weight_t_for(im.dense.weight, dt),
+           weight_t_for(om.dense.weight, dt)]
+    wt_arr = (ctypes.c_void_p * 4)()
+    ld_arr = (ctypes.c_int64 * 4)()
+    for i, w_ in enumerate(wts):
+        if isinstance(w_, SplitOperand):
+            w_ = w_.buf
+        wt_arr[i] = w_.data_ptr() if w_ is not None else None
+        ld_arr[i] = w_.stride(0) if w_ is not None else 0
+    return wts, wt_arr, ld_arr
+
+
 def _layer_plan(layer, pc, dt):
     """the cached pointer arrays of an arena-managed bf16 layer, or None (any other configuration takes the general path)"""
     if dt != torch.bfloat16 or _x3[0]:
@@ -1091,19 +1119,13 @@ def _layer_plan(layer, pc, dt):
     plan = layer.__dict__.get("_vb_plan")
     if plan is not None and plan.sig == sig:
         return plan
-    import ctypes
-    (at, sa, so, im, om), mods, _ = pc
+    sa = pc[0][1]
     arena = getattr(qw, "_vb_arena", None)
     if arena is None or any(getattr(p, "_vb_grad", None) is None or getattr(p, "_vb_arena", None) is not arena for p in params):
         return None
     # the general path's helpers refresh stale shadows as a side effect -- run them once, then take the addresses
-    weights = [weight_for(sa.qkv_weight, dt), sa.qkv_bias, weight_for(so.dense.weight, dt), so.dense.bias.detach(),
-               so.LayerNorm.weight.detach(), so.LayerNorm.bias.detach(),
-               weight_for(im.dense.weight, dt), im.dense.bias.detach(),
-               weight_for(om.dense.weight, dt), om.dense.bias.detach(),
-               om.LayerNorm.weight.detach(), om.LayerNorm.bias.detach()]
-    wts = [weight_t_for(sa.qkv_weight, dt), weight_t_for(so.dense.weight, dt), weight_t_for(im.dense.weight, dt),
-           weight_t_for(om.dense.weight, dt)]
+    weights = _layer_weights(pc, dt)
+    wts, wt_arr, ld_arr = _layer_weights_t(pc, dt)
     g_qkv_w, g_qkv_b, direct_qkv = sa.qkv_grad_targets()
     if not direct_qkv or any(w is None or isinstance(w, SplitOperand) for w in wts):
         return None
@@ -1112,8 +1134,7 @@ def _layer_plan(layer, pc, dt):
     plan = _LayerPlan()
     plan.w_arr = _ptr_array(weights)
     plan.g_arr = _ptr_array(grads)
-    plan.wt_arr = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in wts])
-    plan.ld_arr = (ctypes.c_int64 * 4)(*[w.stride(0) for w in wts])
+    plan.wt_arr, plan.ld_arr = wt_arr, ld_arr
     plan.touched = frozenset(id(p) for p in params)
     plan.arena = arena
     plan.keep = (weights, wts, grads)                       # the views the raw pointers came from
@@ -1163,12 +1184,7 @@ class BertLayerFn(torch.autograd.Function):
         if plan is not None:
             w_arr = plan.w_arr
         else:
-            wqkv = weight_for(sa.qkv_weight, dt)
-            weights = [wqkv, sa.qkv_bias, weight_for(so.dense.weight, dt), so.dense.bias.detach(),
-                       so.LayerNorm.weight.detach(), so.LayerNorm.bias.detach(),
-                       weight_for(im.dense.weight, dt), im.dense.bias.detach(),
-                       weight_for(om.dense.weight, dt), om.dense.bias.detach(),
-                       om.LayerNorm.weight.detach(), om.LayerNorm.bias.detach()]
+            weights = _layer_weights(pc, dt)
             w_arr = _ptr_array(weights)
         seed = next_seed()
         sid = at._sid
@@ -1203,27 +1219,14 @@ class BertLayerFn(torch.autograd.Function):
             _layer_bwd_call(L, rows, code, h2, out, mask_add, dy2, d_in, saved, plan.w_arr, plan.g_arr, plan.wt_arr, plan.ld_arr,
                             ctx.cfg)
             return (d_in.view(B, S, H), None, None, None, None) + _NONE16
-        weights = [weight_for(sa.qkv_weight, dt), sa.qkv_bias, weight_for(so.dense.weight, dt), so.dense.bias.detach(),
-                   so.LayerNorm.weight.detach(), so.LayerNorm.bias.detach(),
-                   weight_for(im.dense.weight, dt), im.dense.bias.detach(),
-                   weight_for(om.dense.weight, dt), om.dense.bias.detach(),
-                   om.LayerNorm.weight.detach(), om.LayerNorm.bias.detach()]
+        weights = _layer_weights(pc, dt)
         g_qkv_w, g_qkv_b, direct_qkv = sa.qkv_grad_targets()
         rest = [so.dense.weight, so.dense.bias, so.LayerNorm.weight, so.LayerNorm.bias, im.dense.weight, im.dense.bias,
                 om.dense.weight, om.dense.bias, om.LayerNorm.weight, om.LayerNorm.bias]
         tg = [grad_target(p) for p in rest]
         grads = [g_qkv_w, g_qkv_b] + [t[0] for t in tg]
         d_in = torch.empty((B * S, H), dtype=dt, device=h2.device)
-        import ctypes
-        wts = [weight_t_for(sa.qkv_weight, dt), weight_t_for(so.dense.weight, dt), weight_t_for(im.dense.weight, dt),
-               weight_t_for(om.dense.weight, dt)]
-        wt_arr = (ctypes.c_void_p * 4)()
-        ld_arr = (ctypes.c_int64 * 4)()
-        for i, w_ in enumerate(wts):
-            if isinstance(w_, SplitOperand):
-                w_ = w_.buf
-            wt_arr[i] = w_.data_ptr() if w_ is not None else None
-            ld_arr[i] = w_.stride(0) if w_ is not None else 0
+        wts, wt_arr, ld_arr = _layer_weights_t(pc, dt)
         _layer_bwd_call(L, rows, code, h2, out, mask_add, dy2, d_in, saved, _ptr_array(weights), _ptr_array(grads), wt_arr, ld_arr,
                         ctx.cfg)
         if direct_qkv:
@@ -1333,6 +1336,71 @@ class EmbeddingsFn(torch.autograd.Function):
                 grad_result(g_pw, d8), grad_result(g_pb, d9))
 
 
+# ---- the MLM head's shared parts: MLMHeadLossFn runs them over all B * S rows and compacts for the decoder's backward,
+# SparseMLMHeadLossFn gathers the labelled rows first and runs everything on those ----------------------------------------------
+def _mlm_head_fwd(x, head, word_weight):
+    """transform GEMM+GELU -> LayerNorm -> tied-decoder GEMM over the rows of x: (pre, t, tn, mean, rstd, fp32 logits, V)"""
+    dt = x.dtype
+    tr = head.transform
+    pre = torch.empty((x.size(0), x.size(1)), dtype=dt, device=x.device)
+    t = linear_fwd(x, weight_for(tr.dense.weight, dt), tr.dense.bias.detach(), VB_ACT_GELU, aux_out=pre)
+    tn, _, mean, rstd = ln_fwd(t, None, tr.LayerNorm.weight.detach(), tr.LayerNorm.bias.detach(),
+                               tr.LayerNorm.variance_epsilon, save_z=False)
+    E = weight_for(word_weight, dt)
+    V = E.size(0)
+    logits = linear_fwd(tn, E, head.bias.detach(), out_dtype=torch.float32)
+    return pre, t, tn, mean, rstd, logits, V
+
+
+def _mlm_dlogits(n_pad, V, dt, device):
+    """d(logits) of n_pad rows; the leading dimension is padded to whole K tiles so that the decoder's dgrad can reduce over it"""
+    return torch.empty((n_pad, round_up(V, 64)), dtype=dt, device=device)[:, :V]
+
+
+def _mlm_decoder_bwd(word_weight, bias, dlogits, H, V, dt, up, wgrad_rows, land):
+    """the tied decoder's backward from compact dlogits [n_pad, V] (zero padding rows): (d(LayerNorm output), dE, d(bias)).
+    wgrad_rows(): the rows of the LayerNorm output that dlogits' rows belong to, [n_pad, H]; land(dtn32): the fp32 dgrad result
+    as the d(LayerNorm output) the transform's backward reads -- each called where its Function has always done that work"""
+    E = weight_for(word_weight, dt)
+    Et = weight_t_for(word_weight, dt)
+    n_pad = dlogits.size(0)
+    tn_c = wgrad_rows()
+    # dgrad over few rows and a 30522-long reduction: split-K (fp32 accumulate) instead of 30 output tiles
+    dtn32 = torch.zeros((n_pad, H), dtype=torch.float32, device=dlogits.device)
+    k_pad = None
+    et_ld = (Et.ld // 2 if isinstance(Et, SplitOperand) else Et.stride(0)) if Et is not None else 0
+    if Et is not None and et_ld == _ld(dlogits) and (et_ld % 64) == 0:
+        k_pad = et_ld                           # both pads are zero: reduce over whole K tiles (LDS-direct)
+    if isinstance(Et, SplitOperand) and (k_pad or V) % 64 != 0:
+        Et = None                               # ragged reduction: the exact fp32 kernels on the master weight
+    if Et is not None:
+        gemm(dlogits, Et, n_pad, H, k_pad or V, out=dtn32, accumulate=True, alpha_dev=up)
+    else:
+        gemm(dlogits, E, n_pad, H, V, b_layout=VB_KSTRIDED, out=dtn32, accumulate=True, alpha_dev=up)
+    dtn = land(dtn32)
+    g_E, d1 = grad_target(word_weight)
+    linear_wgrad(dlogits, tn_c, g_E, alpha_dev=up)
+    g_db, d2 = grad_target(bias)
+    colsum(dlogits, g_db, scale_dev=up)
+    return dtn, grad_result(g_E, d1), grad_result(g_db, d2)
+
+
+def _mlm_transform_bwd(tr, dtn, t, mean, rstd, pre, x):
+    """the transform's backward (LayerNorm, GELU, dense) over the rows of x: (dx, d(dense.weight), d(dense.bias), d(LayerNorm.weight),
+    d(LayerNorm.bias))"""
+    dt = x.dtype
+    g_lw, d3 = grad_target(tr.LayerNorm.weight)
+    g_lb, d4 = grad_target(tr.LayerNorm.bias)
+    dt_, _ = ln_bwd(dtn, t, mean, rstd, tr.LayerNorm.weight.detach(), g_lw, g_lb)
+    dpre = act_bwd(dt_, pre, VB_ACT_GELU)
+    g_tw, d5 = grad_target(tr.dense.weight)
+    g_tb, d6 = grad_target(tr.dense.bias)
+    linear_wgrad(dpre, x, g_tw)
+    colsum(dpre, g_tb)
+    dx = linear_dgrad(dpre, weight_for(tr.dense.weight, dt), wt=weight_t_for(tr.dense.weight, dt))
+    return dx, grad_result(g_tw, d5), grad_result(g_tb, d6), grad_result(g_lw, d3), grad_result(g_lb, d4)
+
+
 @x3_aware
 class MLMHeadLossFn(torch.autograd.Function):
     """BertLMPredictionHead + CrossEntropyLoss(ignore_index=-1), fused (modeling.py:397-401, 417-420,
@@ -1346,14 +1414,7 @@ class MLMHeadLossFn(torch.autograd.Function):
         if not s2.is_contiguous():
             s2 = s2.contiguous()
         dt = s2.dtype
-        tr = head.transform
-        pre = torch.empty((B * S, H), dtype=dt, device=s2.device)
-        t = linear_fwd(s2, weight_for(tr.dense.weight, dt), tr.dense.bias.detach(), VB_ACT_GELU, aux_out=pre)
-        tn, _, mean, rstd = ln_fwd(t, None, tr.LayerNorm.weight.detach(), tr.LayerNorm.bias.detach(),
-                                   tr.LayerNorm.variance_epsilon, save_z=False)
-        E = weight_for(word_weight, dt)
-        V = E.size(0)
-        logits = linear_fwd(tn, E, head.bias.detach(), out_dtype=torch.float32)
+        pre, t, tn, mean, rstd, logits, V = _mlm_head_fwd(s2, head, word_weight)
         loss = None
         dlogits = None
         rows = None
@@ -1367,7 +1428,7 @@ class MLMHeadLossFn(torch.autograd.Function):
             rows = _rows_for(lab)
             n = int(rows.numel())
             n_pad = round_up(max(n, 1), 64)
-            dlogits = torch.empty((n_pad, round_up(V, 64)), dtype=dt, device=s2.device)[:, :V]
+            dlogits = _mlm_dlogits(n_pad, V, dt, s2.device)
             check(_lib.lib().vb_ce_fwd_bwd_rows(_lib.dtype_code(dt), ptr(logits), _ld(logits), ptr(lab), -1,
                                                 ptr(rows) if n else None, n, n_pad, ptr(acc), ptr(loss), ptr(dlogits),
                                                 _ld(dlogits), B * S, V, stream_ptr()), "vb_ce_fwd_bwd_rows")
@@ -1390,46 +1451,26 @@ class MLMHeadLossFn(torch.autograd.Function):
             raise RuntimeError("visualbert_amd: backward through the MLM head needs masked_lm_labels")
         B, S, H, V = ctx.cfg
         head = ctx.head
-        tr = head.transform
         dt = s2.dtype
         up = _upstream_scalar(dloss)
-        E = weight_for(ctx.word_weight, dt)
-        Et = weight_t_for(ctx.word_weight, dt)
         n, n_pad = int(rows.numel()), dlogits.size(0)
-        # compact operands: dlogits is [n_pad, V] (rows of the masked tokens, zero padding), tn_c the same rows of tn
-        tn_c = torch.zeros((n_pad, H), dtype=dt, device=tn.device)
-        if n:
-            tn_c[:n] = tn.index_select(0, rows)
-        # dgrad over few rows and a 30522-long reduction: split-K (fp32 accumulate) instead of 30 output tiles
-        dtn_c = torch.zeros((n_pad, H), dtype=torch.float32, device=tn.device)
-        k_pad = None
-        et_ld = (Et.ld // 2 if isinstance(Et, SplitOperand) else Et.stride(0)) if Et is not None else 0
-        if Et is not None and et_ld == _ld(dlogits) and (et_ld % 64) == 0:
-            k_pad = et_ld                           # both pads are zero: reduce over whole K tiles (LDS-direct)
-        if isinstance(Et, SplitOperand) and (k_pad or V) % 64 != 0:
-            Et = None                               # ragged reduction: the exact fp32 kernels on the master weight
-        if Et is not None:
-            gemm(dlogits, Et, n_pad, H, k_pad or V, out=dtn_c, accumulate=True, alpha_dev=up)
-        else:
-            gemm(dlogits, E, n_pad, H, V, b_layout=VB_KSTRIDED, out=dtn_c, accumulate=True, alpha_dev=up)
-        dtn = torch.zeros((B * S, H), dtype=dt, device=tn.device)
-        if n:
-            dtn.index_copy_(0, rows, dtn_c[:n].to(dt))
-        g_E, d1 = grad_target(ctx.word_weight)
-        linear_wgrad(dlogits, tn_c, g_E, alpha_dev=up)
-        g_db, d2 = grad_target(head.bias)
-        colsum(dlogits, g_db, scale_dev=up)
-        g_lw, d3 = grad_target(tr.LayerNorm.weight)
-        g_lb, d4 = grad_target(tr.LayerNorm.bias)
-        dt_, _ = ln_bwd(dtn, t, mean, rstd, tr.LayerNorm.weight.detach(), g_lw, g_lb)
-        dpre = act_bwd(dt_, pre, VB_ACT_GELU)
-        g_tw, d5 = grad_target(tr.dense.weight)
-        g_tb, d6 = grad_target(tr.dense.bias)
-        linear_wgrad(dpre, s2, g_tw)
-        colsum(dpre, g_tb)
-        dseq = linear_dgrad(dpre, weight_for(tr.dense.weight, dt), wt=weight_t_for(tr.dense.weight, dt))
-        return (dseq.view(B, S, H), None, None, grad_result(g_E, d1), grad_result(g_db, d2), grad_result(g_tw, d5),
-                grad_result(g_tb, d6), grad_result(g_lw, d3), grad_result(g_lb, d4))
+
+        def tn_rows():
+            # compact operands: dlogits is [n_pad, V] (rows of the masked tokens, zero padding), tn_c the same rows of tn
+            tn_c = torch.zeros((n_pad, H), dtype=dt, device=tn.device)
+            if n:
+                tn_c[:n] = tn.index_select(0, rows)
+            return tn_c
+
+        def scatter(dtn_c):
+            dtn = torch.zeros((B * S, H), dtype=dt, device=tn.device)
+            if n:
+                dtn.index_copy_(0, rows, dtn_c[:n].to(dt))
+            return dtn
+
+        dtn, r_E, r_db = _mlm_decoder_bwd(ctx.word_weight, head.bias, dlogits, H, V, dt, up, tn_rows, scatter)
+        dseq, r_tw, r_tb, r_lw, r_lb = _mlm_transform_bwd(head.transform, dtn, t, mean, rstd, pre, s2)
+        return (dseq.view(B, S, H), None, None, r_E, r_db, r_tw, r_tb, r_lw, r_lb)
 
 
 @x3_aware
@@ -1445,7 +1486,6 @@ class SparseMLMHeadLossFn(torch.autograd.Function):
         B, S, H = seq.shape
         s2 = seq.reshape(B * S, H)
         dt = s2.dtype
-        tr = head.transform
         lab = labels.reshape(-1).contiguous()
         rows = _rows_for(lab)
         n = int(rows.numel())
@@ -1455,16 +1495,10 @@ class SparseMLMHeadLossFn(torch.autograd.Function):
         if n:
             s_c[:n] = s2.index_select(0, rows)
             lab_c[:n] = lab.index_select(0, rows)
-        pre = torch.empty((n_pad, H), dtype=dt, device=s2.device)
-        t = linear_fwd(s_c, weight_for(tr.dense.weight, dt), tr.dense.bias.detach(), VB_ACT_GELU, aux_out=pre)
-        tn, _, mean, rstd = ln_fwd(t, None, tr.LayerNorm.weight.detach(), tr.LayerNorm.bias.detach(),
-                                   tr.LayerNorm.variance_epsilon, save_z=False)
-        E = weight_for(word_weight, dt)
-        V = E.size(0)
-        logits = linear_fwd(tn, E, head.bias.detach(), out_dtype=torch.float32)
+        pre, t, tn, mean, rstd, logits, V = _mlm_head_fwd(s_c, head, word_weight)
         acc = torch.empty(66, dtype=torch.float32, device=s2.device)
         loss = torch.empty(1, dtype=torch.float32, device=s2.device)
-        dlogits = torch.empty((n_pad, round_up(V, 64)), dtype=dt, device=s2.device)[:, :V]
+        dlogits = _mlm_dlogits(n_pad, V, dt, s2.device)
         check(_lib.lib().vb_ce_fwd_bwd(_lib.dtype_code(dt), ptr(logits), _ld(logits), ptr(lab_c), -1, ptr(acc), ptr(loss),
                                        ptr(dlogits), _ld(dlogits), n_pad, V, stream_ptr()), "vb_ce_fwd_bwd")
         ctx.head, ctx.word_weight = head, word_weight
@@ -1480,42 +1514,14 @@ class SparseMLMHeadLossFn(torch.autograd.Function):
         s_c, pre, t, tn, mean, rstd, dlogits, rows = ctx.saved_tensors
         B, S, H, V, n = ctx.cfg
         head = ctx.head
-        tr = head.transform
         dt = s_c.dtype
-        n_pad = s_c.size(0)
         up = _upstream_scalar(dloss)
-        E = weight_for(ctx.word_weight, dt)
-        Et = weight_t_for(ctx.word_weight, dt)
-        dtn32 = torch.zeros((n_pad, H), dtype=torch.float32, device=s_c.device)
-        k_pad = None
-        et_ld = (Et.ld // 2 if isinstance(Et, SplitOperand) else Et.stride(0)) if Et is not None else 0
-        if Et is not None and et_ld == _ld(dlogits) and (et_ld % 64) == 0:
-            k_pad = et_ld
-        if isinstance(Et, SplitOperand) and (k_pad or V) % 64 != 0:
-            Et = None                               # ragged reduction: the exact fp32 kernels on the master weight
-        if Et is not None:
-            gemm(dlogits, Et, n_pad, H, k_pad or V, out=dtn32, accumulate=True, alpha_dev=up)
-        else:
-            gemm(dlogits, E, n_pad, H, V, b_layout=VB_KSTRIDED, out=dtn32, accumulate=True, alpha_dev=up)
-        dtn = dtn32.to(dt)
-        g_E, d1 = grad_target(ctx.word_weight)
-        linear_wgrad(dlogits, tn, g_E, alpha_dev=up)
-        g_db, d2 = grad_target(head.bias)
-        colsum(dlogits, g_db, scale_dev=up)
-        g_lw, d3 = grad_target(tr.LayerNorm.weight)
-        g_lb, d4 = grad_target(tr.LayerNorm.bias)
-        dt_, _ = ln_bwd(dtn, t, mean, rstd, tr.LayerNorm.weight.detach(), g_lw, g_lb)
-        dpre = act_bwd(dt_, pre, VB_ACT_GELU)
-        g_tw, d5 = grad_target(tr.dense.weight)
-        g_tb, d6 = grad_target(tr.dense.bias)
-        linear_wgrad(dpre, s_c, g_tw)
-        colsum(dpre, g_tb)
-        dseq_c = linear_dgrad(dpre, weight_for(tr.dense.weight, dt), wt=weight_t_for(tr.dense.weight, dt))
+        dtn, r_E, r_db = _mlm_decoder_bwd(ctx.word_weight, head.bias, dlogits, H, V, dt, up, lambda: tn, lambda dtn32: dtn32.to(dt))
+        dseq_c, r_tw, r_tb, r_lw, r_lb = _mlm_transform_bwd(head.transform, dtn, t, mean, rstd, pre, s_c)
         dseq = torch.zeros((B * S, H), dtype=dt, device=s_c.device)
         if n:
             dseq.index_copy_(0, rows, dseq_c[:n])
-        return (dseq.view(B, S, H), None, None, grad_result(g_E, d1), grad_result(g_db, d2), grad_result(g_tw, d5),
-                grad_result(g_tb, d6), grad_result(g_lw, d3), grad_result(g_lb, d4))
+        return (dseq.view(B, S, H), None, None, r_E, r_db, r_tw, r_tb, r_lw, r_lb)
 
 
 @x3_aware
