@@ -91,6 +91,8 @@ int vb_stream_set_scratch(void* stream, void* scratch, int64_t bytes);
  * GEMM with fused epilogue.   C[M,N] = epi( alpha * sum_k Aop[m,k] * Bop[n,k] )
  *   a_layout / b_layout: VB_KCONTIG  -> operand stored [rows][K]  (ld = row pitch)
  *                        VB_KSTRIDED -> operand stored [K][rows]  (ld = k pitch)
+ *   Three of the four layout pairs have kernels: A and B K-contiguous (forward), A K-contiguous with B K-strided (dgrad), both
+ *   K-strided (wgrad).  A K-strided with B K-contiguous returns VB_ERR_UNSUPPORTED and writes nothing.
  *   epi: + bias[n] (fp32, may be NULL) -> act -> + addend[m,n] (T, may be NULL) -> (+= C if accumulate)
  *   act: VB_ACT_GELU also writes the pre-activation (T) to aux_out when non-NULL;
  *        VB_ACT_GELU_GRAD multiplies by gelu'(aux_in[m,n]) (T);  VB_ACT_TANH applies tanh.

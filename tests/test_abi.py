@@ -37,6 +37,38 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert b"gfx950" in lib.vb_version()
 
 
+#: entry points that no GPU test calls by name, each with the reason: they launch no kernel of their own or need several ranks
+NO_KERNEL_TEST = {
+    "vb_version": "returns a static string; read without a device by test_library_loads_and_exports_every_declared_symbol",
+    "vb_stream_set_scratch": "host-side table entry plus one memset; _lib.stream_ptr() registers a buffer for every stream a test uses, "
+                             "and test_kernels.py's split-K tests depend on it",
+    "vb_comm_unique_id": "RCCL bootstrap, no kernel; run with one rank through visualbert_amd.parallel by tests/test_data_parallel_cpu.py",
+    "vb_comm_init": "RCCL bootstrap, a collective over the ranks; same one-rank run, more ranks need more GPUs than a test may ask for",
+    "vb_comm_destroy": "frees the communicator that only vb_comm_init creates; same one-rank run",
+    "vb_allreduce_bucket": "an RCCL collective, no kernel of this library; same one-rank run, bench.py --gpus N for more ranks",
+}
+
+
+def test_every_entry_point_has_a_kernel_test_or_a_reason():
+    """the ledger behind "every C-ABI entry point has a test on its own inputs": each vb_* symbol of the public header is called by
+    name (L.vb_xyz(...)) in a tests/test_*.py that holds GPU tests, or is listed in NO_KERNEL_TEST with the reason.  A new entry point
+    fails here until it has one or the other; a listed name that gains a test must leave the list."""
+    import glob
+    called = {}
+    for path in sorted(glob.glob(os.path.join(ROOT, "tests", "test_*.py"))):
+        txt = open(path).read()
+        if os.path.samefile(path, __file__) or "pytest.mark.gpu" not in txt:      # (this file names the mark but has no GPU test)
+            continue
+        for name in set(re.findall(r"\.(vb_[a-z0-9_]+)\s*\(", txt)):
+            called.setdefault(name, []).append(os.path.basename(path))
+    syms = header_symbols()
+    missing = [s for s in syms if s not in called and s not in NO_KERNEL_TEST]
+    assert not missing, "no GPU test calls these entry points by name and NO_KERNEL_TEST gives no reason: %s" % missing
+    stale = [s for s in NO_KERNEL_TEST if s not in syms or s in called]
+    assert not stale, "NO_KERNEL_TEST lists names that are tested or no longer exist: %s" % stale
+    assert all(isinstance(r, str) and len(r) > 10 for r in NO_KERNEL_TEST.values())
+
+
 def test_layer_backward_insists_on_the_forward_output():
     """argument checks only (they run on the host, before any launch): with H <= 768 the LayerNorm forward may have skipped its pre-LN
     sum, so the backward cannot run without h_out; the saved-workspace size answers without a device too"""

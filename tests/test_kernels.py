@@ -1,6 +1,9 @@
-"""Per-kernel parity: every C-ABI entry point against plain torch fp32 maths on the same inputs.
-fp32 kernels must agree to fp32 round-off; bf16 kernels are compared with the same maths on
-bf16-rounded inputs at a bf16-sized tolerance (stated per test)."""
+"""Per-kernel parity: the GEMM, attention, LayerNorm, embedding, cross-entropy, weight-gradient and grounding-head entry points of
+the C ABI against plain torch fp32 maths on the same inputs.  fp32 kernels must agree to fp32 round-off; bf16 kernels are compared
+with the same maths on bf16-rounded inputs at a bf16-sized tolerance (stated per test).
+The remaining entry points (column sums, activation backward, casts, the VQA loss and row gather, input preparation, attention
+probabilities, the rebuild LayerNorm pair, the small-linear heads, the shadow refreshes) and the edge shapes of cross-entropy and
+GEMM are in tests/test_kernel_edges.py, against float64; tests/test_abi.py keeps the ledger of which entry point is called where."""
 import ctypes
 import math
 
