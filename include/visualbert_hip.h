@@ -253,6 +253,31 @@ int vb_ce_fwd_bwd_rows(int dtype, const float* logits, int64_t ld_logits, const 
 int vb_kldiv_fwd_bwd(const float* logits, int64_t ld_logits, const float* target, int64_t ld_target,
                      float* loss, float* score, float* dlogits, int64_t ld_dlogits, int M, int V, void* stream);
 
+/* The masked-region objective of the sibling LXRT model: three per-region losses and their gradients in one sweep over one
+ * score matrix.  scores: T [M, ld_scores] (T = fp32 or bf16 by dtype), M = B * R regions; its columns are three adjacent
+ * segments -- object logits [0, n_obj), attribute logits [n_obj, n_obj + n_attr), feature prediction [n_obj + n_attr,
+ * n_obj + n_attr + n_feat) -- then padding up to ld_scores whose content does not matter.  A segment of width 0 switches its
+ * loss off (its label / confidence / target pointers may then be NULL).  At most 4096 columns in all (VB_ERR_UNSUPPORTED beyond).
+ *   obj / attr: l_r = CrossEntropy(scores[r, segment], label[r]) with ignore_index = -1; a label outside [0, n) is treated as
+ *     ignored too (as vb_ce_fwd_bwd does), l_r = 0 for an ignored row; loss = w * (1 / M) * sum_r conf[r] * l_r -- the mean is
+ *     over ALL M rows, so nothing is NaN when no row counts.
+ *   feat: e = scores[r, segment] - feat_target[r, :] (fp32 [M, ld_target]); SmoothL1 with beta = 1 (0.5 e^2 if |e| < 1, else
+ *     |e| - 0.5), mean over n_feat; loss = w * (1 / M) * sum_r feat_conf[r] * rowmean.
+ *   losses: fp32[4] = {obj, attr, feat, their sum}.  ws: fp32[vb_visual_loss_ws_floats(M)] scratch -- every row stores its three
+ *     terms there and a second single-workgroup launch adds them in a fixed order (no float atomics): bit-identical from run to run.
+ *   dscores (T [M, ld_dscores], may be NULL, may alias scores): d losses[3] / d scores for an upstream gradient of 1 --
+ *     w / M * conf[r] * (softmax - onehot) on counted rows, w / (M n_feat) * feat_conf[r] * clamp(e, -1, 1), zero bits wherever the
+ *     row's label is ignored or its confidence / mask is 0, and zeroed pad columns up to ld_dscores (the vb_ce_fwd_bwd contract).
+ *     A row whose three weights are all zero is never read.
+ * Replaces the loss lines of LXRTPretraining.forward (unsupervised_visualbert/src/lxrt/modeling.py:1391-1420: CrossEntropyLoss
+ * (ignore_index=-1, reduction='none'), SmoothL1Loss(reduction='none').mean(1), (loss * mask_conf).mean() * weight) and autograd. */
+int64_t vb_visual_loss_ws_floats(int M);
+int vb_visual_loss_fwd_bwd(int dtype, const void* scores, int64_t ld_scores, int n_obj, int n_attr, int n_feat,
+                           const int64_t* obj_label, const float* obj_conf, const int64_t* attr_label, const float* attr_conf,
+                           const float* feat_target, int64_t ld_target, const float* feat_conf,
+                           float w_obj, float w_attr, float w_feat, float* ws, float* losses,
+                           void* dscores, int64_t ld_dscores, int M, void* stream);
+
 /* Heads with a tiny output width (seq_relationship 768->2, modeling.py:451; NLVR2 768->2, :1558).
  * x: T [M,K]; W: fp32 master [N,K]; y / dy: fp32 [M,N].  Backward: dx (T, overwritten, may be NULL),
  * dW / db fp32 ACCUMULATED (may be NULL); scale_dev: optional fp32 device scalar (upstream gradient). */

@@ -48,6 +48,8 @@ SIGNATURES = {
     "vb_ce_fwd_bwd": (_i, [_i, _p, _i64, _p, _i, _p, _p, _p, _i64, _i, _i, _p]),
     "vb_ce_fwd_bwd_rows": (_i, [_i, _p, _i64, _p, _i, _p, _i, _i, _p, _p, _p, _i64, _i, _i, _p]),
     "vb_kldiv_fwd_bwd": (_i, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i, _i, _p]),
+    "vb_visual_loss_ws_floats": (_i64, [_i]),
+    "vb_visual_loss_fwd_bwd": (_i, [_i, _p, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _i64, _p, _f, _f, _f, _p, _p, _p, _i64, _i, _p]),
     "vb_small_linear_fwd": (_i, [_i, _p, _i64, _p, _p, _p, _i, _i, _i, _p]),
     "vb_small_linear_bwd": (_i, [_i, _p, _p, _i64, _p, _p, _i64, _p, _p, _p, _i, _i, _i, _p]),
     "vb_bert_adam_step": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p, _p, _f, _f, _f, _f, _f, _f, _f, _f, _i, _p]),

@@ -92,6 +92,34 @@ def mask_tokens(input_ids, maskable, vocab_size, mask_id, probability=0.15, gene
     return out, labels
 
 
+def mask_region_features(features, valid, rate=0.15, generator=None, uniforms=None, random_features=None):
+    """Whole-batch form of the sibling's per-region loop `random_mask_features`
+    (unsupervised_visualbert/src/pretrain/lxmert_data.py:558-583): a region is selected with probability `rate`; of the selected
+    ones 80 % have their feature zeroed, 10 % get a random feature, 10 % keep theirs; feat_mask is 1 for every selected region
+    (the regions whose feature / class the objective must predict) and 0 elsewhere.  The loop draws one uniform per region and
+    reuses it (prob /= rate) to pick among the three outcomes -- so does this function, which makes it element-for-element
+    identical to the loop when given the same uniforms (`uniforms` [B, R], `random_features` [B, R, Dv]: injected draws for
+    tests; otherwise from `generator`, the random features then being features of randomly drawn regions of this batch).
+
+    features: float [B, R, Dv]; valid: bool [B, R] (False for padding regions, which the reference never passes to the loop:
+    they are never selected).  Returns (masked features, feat_mask fp32 [B, R]).  The reference's `inbatch_random` variant
+    (feat_mask 2.0 as a marker) is not offered."""
+    B, R = features.shape[:2]
+    if uniforms is None:
+        uniforms = torch.rand((B, R), generator=generator, dtype=torch.float64)
+    if random_features is None:
+        idx = torch.randint(0, B * R, (B * R,), generator=generator, dtype=torch.int64)
+        random_features = features.reshape(B * R, -1).index_select(0, idx.to(features.device)).reshape(features.shape)
+    uniforms = uniforms.to(features.device)
+    sel = (uniforms < rate) & valid.to(torch.bool)
+    u2 = uniforms / rate
+    to_zero = sel & (u2 < 0.8)
+    to_rand = sel & (u2 >= 0.8) & (u2 < 0.9)
+    out = torch.where(to_zero.unsqueeze(-1), torch.zeros_like(features), features)
+    out = torch.where(to_rand.unsqueeze(-1), random_features.to(features.dtype), out)
+    return out, sel.to(torch.float32)
+
+
 def collate_pretraining(ids_a, ids_b, is_correct, features, vocab_size, mask_id, cls_id, sep_id, probability=0.15,
                         generator=None, uniforms=None, random_ids=None, pin=True):
     """One pre-training batch from tokenised caption pairs and per-image region features, built with whole-batch tensor

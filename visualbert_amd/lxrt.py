@@ -20,7 +20,13 @@ These are stand-alone modules (no flat parameter arena): gradients reach `.grad`
 
 The reference's own constructor reaches the l / r / x stack only through an `assert(0)` (lxrt/modeling.py:803-804): no
 argument set builds it there, but its forward (:893-905) is well defined, and tests/golden/base_lxrt_encoder.npz pins this
-class against that forward run on the reference's own blocks (the golden generator assembles the module around the assert).  `output_attention` (returning the probabilities) is not offered: NotImplementedError, never silent."""
+class against that forward run on the reference's own blocks (the golden generator assembles the module around the assert).  `output_attention` (returning the probabilities) is not offered: NotImplementedError, never silent.
+
+  BertVisualObjHead                     :971-996   transform + one decoder per visual loss, into ONE score buffer
+  LXRTPretrainingHeads                  :1297-1420 the heads of LXRTPretraining (`cls`, `obj_predict_head`) and its loss lines:
+                                                   masked LM, image-text match and the masked-region objective -- object class,
+                                                   attribute class, feature regression per region, each weighted by a per-region
+                                                   confidence / mask -- through ops.VisualLossFn (vb_visual_loss_fwd_bwd)"""
 import torch
 from torch import nn
 
@@ -274,6 +280,132 @@ class _PadColumns(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         return g[:, :ctx.k].contiguous(), None
+
+
+#: default output widths of the visual decoders: 1600 detector object classes, 400 attribute classes, the 2048-d region feature
+#: (the reference's VISUAL_CONFIG.visual_loss_config)
+VISUAL_LOSS_SIZES = {"obj": 1600, "attr": 400, "feat": 2048}
+
+
+def _visual_loss_keys(visual_losses):
+    keys = [k for k in str(visual_losses).split(",") if k]
+    for k in keys:
+        if k not in ops.VISUAL_SEGMENTS:
+            raise NotImplementedError("visual loss %r: the objective kernel implements %s" % (k, ", ".join(ops.VISUAL_SEGMENTS)))
+    if not keys or len(set(keys)) != len(keys):
+        raise ValueError("visual_losses %r: one to three different keys of %s" % (visual_losses, ops.VISUAL_SEGMENTS))
+    return keys
+
+
+class BertVisualObjHead(nn.Module):
+    """lxrt/modeling.py:971-996, same state-dict keys (transform.dense / transform.LayerNorm / decoder_dict.<key>).  The
+    reference reads the decoder widths from its global VISUAL_CONFIG; here they are an argument (`sizes`, per key).
+
+    forward(hidden_states [.., H]) returns ONE score buffer T [M, ld] (M = rows of hidden_states, ld a multiple of 64) instead
+    of the reference's dict of three tensors: its column blocks are the decoders' outputs in the order ops.VISUAL_SEGMENTS
+    (obj | attr | feat, absent keys left out; the default visual_losses order) -- the layout ops.VisualLossFn reads.
+    `segment_widths()` gives (n_obj, n_attr, n_feat); `scores_dict(buffer)` the reference's dict as views."""
+
+    def __init__(self, config, visual_losses="obj,attr,feat", sizes=None):
+        super(BertVisualObjHead, self).__init__()
+        from .modeling import BertPredictionHeadTransform
+        self.transform = BertPredictionHeadTransform(config)
+        self.visual_losses = _visual_loss_keys(visual_losses)
+        sizes = dict(VISUAL_LOSS_SIZES if sizes is None else sizes)
+        self.sizes = {k: int(sizes[k]) for k in self.visual_losses}
+        for k, n in self.sizes.items():
+            if n <= 0 or n % 8:
+                raise NotImplementedError("decoder %r of width %d: column blocks of the score buffer start on 16-byte boundaries "
+                                          "(widths are multiples of 8)" % (k, n))
+        self.decoder_dict = nn.ModuleDict({k: nn.Linear(config.hidden_size, self.sizes[k]) for k in self.visual_losses})
+
+    def segment_widths(self):
+        return tuple(self.sizes.get(k, 0) for k in ops.VISUAL_SEGMENTS)
+
+    def scores_dict(self, scores):
+        out, off = {}, 0
+        for k in ops.VISUAL_SEGMENTS:
+            if k in self.sizes:
+                out[k] = scores[:, off:off + self.sizes[k]]
+                off += self.sizes[k]
+        return out
+
+    def forward(self, hidden_states):
+        h = self.transform(hidden_states)
+        segs = tuple(i for i, k in enumerate(ops.VISUAL_SEGMENTS) if k in self.sizes)
+        params = []
+        for i in segs:
+            lin = self.decoder_dict[ops.VISUAL_SEGMENTS[i]]
+            params += [lin.weight, lin.bias]
+        return ops.VisualDecoderFn.apply(h, segs, *params)
+
+
+class LXRTPretrainingHeads(nn.Module):
+    """The heads and the loss lines of LXRTPretraining (lxrt/modeling.py:1297-1420) over the encoder's outputs: `cls` (masked LM
+    with the decoder tied to `word_embedding_weight`, image-text match) and `obj_predict_head` (masked-region modelling), under
+    the reference's attribute names.  forward returns (total_loss, losses [1, n], losses_dict) with the reference's terms, order
+    and names: "Masked LM", "Matches", then the keys of visual_losses.  obj_labels: {key: (label, mask_conf)} -- int class ids
+    [B, R] for obj / attr, the fp32 target feature [B, R, D] for feat, one confidence / mask per region.  Every visual term is
+    (loss_r * mask_conf_r).mean() * loss_weight (the reference's 1 / 0.15; its `weight_disable` is loss_weight=1.0).
+    Not offered (NotImplementedError, never silently different): the QA answer head (its LayerNorm is 2 H wide, beyond the
+    LayerNorm kernels), the tag / symbolic heads, lxmert_style_nlvr and the `kl` loss form."""
+
+    def __init__(self, config, word_embedding_weight, task_mask_lm=True, task_matched=True, task_obj_predict=True,
+                 visual_losses="obj,attr,feat", loss_weight=1 / 0.15, sizes=None, task_qa=False,
+                 use_tag_symbolic_embedding=False, lxmert_style_nlvr=False, loss_forms=None):
+        super(LXRTPretrainingHeads, self).__init__()
+        from .modeling import BertPreTrainingHeads
+        if task_qa:
+            raise NotImplementedError("task_qa: the answer head's LayerNorm is 2 x hidden_size wide, beyond the LayerNorm kernels")
+        if use_tag_symbolic_embedding:
+            raise NotImplementedError("use_tag_symbolic_embedding: the tag / symbolic heads are not implemented")
+        if lxmert_style_nlvr:
+            raise NotImplementedError("lxmert_style_nlvr is not implemented")
+        forms = {"obj": "ce", "attr": "ce", "feat": "l2"}
+        for k, f in (loss_forms or {}).items():
+            if forms.get(k) != f:
+                raise NotImplementedError("loss form %r for %r: the kernel implements ce for obj / attr and l2 for feat" % (f, k))
+        self.task_mask_lm, self.task_matched, self.task_obj_predict = task_mask_lm, task_matched, task_obj_predict
+        self.visual_losses = _visual_loss_keys(visual_losses)
+        self.loss_weight = float(loss_weight)
+        self.cls = BertPreTrainingHeads(config, word_embedding_weight)
+        if task_obj_predict:
+            self.obj_predict_head = BertVisualObjHead(config, visual_losses, sizes=sizes)
+
+    def forward(self, lang_output, pooled_output, visn_output, masked_lm_labels=None, matched_label=None, obj_labels=None):
+        total_loss = None
+        losses, losses_dict = [], {}
+
+        def add(name, term):
+            nonlocal total_loss
+            total_loss = term if total_loss is None else total_loss + term
+            losses.append(term.detach())
+            losses_dict[name] = term.detach()
+
+        if masked_lm_labels is not None and self.task_mask_lm:
+            pred = self.cls.predictions
+            tr = pred.transform
+            _, mlm_loss = ops.MLMHeadLossFn.apply(lang_output, masked_lm_labels.contiguous(), pred, pred.decoder.weight, pred.bias,
+                                                  tr.dense.weight, tr.dense.bias, tr.LayerNorm.weight, tr.LayerNorm.bias)
+            add("Masked LM" if visn_output is not None else "Text Only Masked LM", mlm_loss)
+        if matched_label is not None and self.task_matched and pooled_output is not None:
+            _, matched_loss = ops.SmallLinearCEFn.apply(pooled_output, matched_label.reshape(-1), -1,
+                                                        self.cls.seq_relationship.weight, self.cls.seq_relationship.bias)
+            add("Matches", matched_loss)
+        if obj_labels is not None and self.task_obj_predict:
+            head = self.obj_predict_head
+            scores = head(visn_output)
+            n_obj, n_attr, n_feat = head.segment_widths()
+            args = []
+            for k in ops.VISUAL_SEGMENTS:
+                args += list(obj_labels[k]) if k in head.sizes else [None, None]
+            w = self.loss_weight
+            visn = ops.VisualLossFn.apply(scores, n_obj, n_attr, n_feat, *args, w, w, w)
+            for k in self.visual_losses:
+                add(k, visn[ops.VISUAL_SEGMENTS.index(k)])
+        if total_loss is None:
+            total_loss = torch.zeros((), device=lang_output.device if lang_output is not None else visn_output.device)
+        return total_loss, torch.stack(losses).unsqueeze(0) if losses else torch.zeros((1, 0)), losses_dict
 
 
 def lxrt_init_weights(module, initializer_range=0.02):

@@ -1716,3 +1716,137 @@ class FlickrHeadLossFn(torch.autograd.Function):
                                       ptr(dseq), B, S, E, H, stream_ptr()), "vb_scatter_index_rows")
         return (dseq.view(B, S, H), None, None, None, None, None, grad_result(gwq, d1), grad_result(gbq, d2),
                 grad_result(gwk, d3), grad_result(gbk, d4))
+
+
+# ------------------------------------------------------------------------------------------------
+# the masked-region objective of the sibling LXRT model (lxrt.BertVisualObjHead / LXRTPretrainingHeads)
+# ------------------------------------------------------------------------------------------------
+VISUAL_SEGMENTS = ("obj", "attr", "feat")           # column order of the score buffer: the order vb_visual_loss_fwd_bwd reads
+
+
+@x3_aware
+class VisualDecoderFn(torch.autograd.Function):
+    """The decoders of BertVisualObjHead (unsupervised_visualbert/src/lxrt/modeling.py:986-996): up to three nn.Linear of ONE
+    input, written into adjacent column blocks of ONE score buffer [M, ld] (ld a multiple of 64; pad columns are never
+    initialised and never read).  segs: which of VISUAL_SEGMENTS the (weight, bias) pairs in *params are, ascending.
+    When the buffer goes straight into VisualLossFn, that node leaves its upstream scalars here (`_vb_alpha`) and hands the
+    gradient of an upstream 1 on: the backward GEMMs apply the scalar through alpha_dev, as the MLM head does."""
+
+    @staticmethod
+    def forward(ctx, x, segs, *params):
+        x2 = as2d(x)
+        if not x2.is_contiguous():
+            x2 = x2.contiguous()
+        dt = x2.dtype
+        M, K = x2.shape
+        widths = [int(params[2 * i].size(0)) for i in range(len(segs))]
+        scores = torch.empty((M, round_up(sum(widths), 64)), dtype=dt, device=x2.device)
+        off = 0
+        for i, n in enumerate(widths):
+            w, b = params[2 * i], params[2 * i + 1]
+            gemm(x2, weight_for(w, dt), M, n, K, out=scores[:, off:off + n], bias=b.detach())
+            off += n
+        ctx.segs, ctx.widths, ctx.params, ctx.x_shape = tuple(segs), widths, params, x.shape
+        ctx._vb_takes_alpha = True
+        ctx._vb_alpha = None
+        ctx.save_for_backward(x2)
+        return scores
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, = ctx.saved_tensors
+        dt = x2.dtype
+        M, K = x2.shape
+        alpha = ctx._vb_alpha                       # fp32 [3] on the device (per segment), or None: dy is the whole gradient
+        if dy.dtype != dt:
+            dy = dy.to(dt)
+        if dy.stride(1) != 1 or (dy.stride(0) % 8) != 0 or (dy.data_ptr() % 16) != 0:
+            t = torch.zeros((M, round_up(dy.size(1), 64)), dtype=dt, device=dy.device)[:, :dy.size(1)]
+            t.copy_(dy)
+            dy = t
+        dx32 = torch.zeros((M, K), dtype=torch.float32, device=x2.device) if ctx.needs_input_grad[0] else None
+        grads = []
+        off = 0
+        for i, n in enumerate(ctx.widths):
+            w, b = ctx.params[2 * i], ctx.params[2 * i + 1]
+            a = alpha[ctx.segs[i]:ctx.segs[i] + 1] if alpha is not None else None
+            dy_k = dy[:, off:off + n]
+            off += n
+            if dx32 is not None:
+                wt = weight_t_for(w, dt)
+                if isinstance(wt, SplitOperand) and (n % 64 != 0 or wt.ld // 2 < n):
+                    wt = None
+                if wt is not None:
+                    gemm(dy_k, wt, M, K, n, out=dx32, accumulate=True, alpha_dev=a)
+                else:
+                    gemm(dy_k, weight_for(w, dt), M, K, n, b_layout=VB_KSTRIDED, out=dx32, accumulate=True, alpha_dev=a)
+            gw, d1 = grad_target(w)
+            linear_wgrad(dy_k, x2, gw, alpha_dev=a)
+            gb, d2 = grad_target(b)
+            colsum(dy_k, gb, scale_dev=a)
+            grads += [grad_result(gw, d1), grad_result(gb, d2)]
+        dx = None
+        if dx32 is not None:
+            dx = (dx32 if dt == torch.float32 else dx32.to(dt)).view(ctx.x_shape)
+        return (dx, None) + tuple(grads)
+
+
+class VisualLossFn(torch.autograd.Function):
+    """The three masked-region losses in ONE call (vb_visual_loss_fwd_bwd; unsupervised_visualbert/src/lxrt/modeling.py:1391-1420).
+    scores: T [M, ld], columns obj | attr | feat of widths n_obj, n_attr, n_feat (0 = that loss is off), then padding.
+    Returns fp32 [4] = (obj, attr, feat, their sum), each (loss_r * conf_r).mean() * weight.
+
+    The gradient is written IN PLACE over `scores` during the forward (for an upstream gradient of 1): after this call the buffer
+    no longer holds the scores -- nothing outside the objective reads them.  When scores does not require a gradient (e.g. under
+    torch.no_grad()) no gradient is written and scores stays intact.  Backward hands that stored gradient on; the upstream
+    scalars d(total)/d(losses[k]) + d(total)/d(losses[3]) stay on the device (no host sync): a VisualDecoderFn producer
+    applies them inside its backward GEMMs, any other producer receives the column blocks scaled here."""
+
+    @staticmethod
+    def forward(ctx, scores, n_obj, n_attr, n_feat, obj_label, obj_conf, attr_label, attr_conf, feat_target, feat_conf,
+                w_obj, w_attr, w_feat):
+        if scores.dim() != 2 or scores.stride(1) != 1:
+            raise RuntimeError("visualbert_amd.VisualLossFn: scores must be a row-major [M, ld] matrix")
+        L = _lib.lib()
+        M = scores.size(0)
+        dev = scores.device
+
+        def vec(t, dtype):
+            return None if t is None else t.reshape(-1).to(dtype).contiguous()
+
+        ol, al = vec(obj_label, torch.int64), vec(attr_label, torch.int64)
+        oc, ac, fc = vec(obj_conf, torch.float32), vec(attr_conf, torch.float32), vec(feat_conf, torch.float32)
+        ft = feat_target.reshape(M, n_feat).to(torch.float32).contiguous() if n_feat > 0 else None
+        for n, tensors in ((n_obj, (ol, oc)), (n_attr, (al, ac)), (n_feat, (ft, fc))):
+            if n > 0 and any(t is None or t.size(0) != M for t in tensors):
+                raise RuntimeError("visualbert_amd.VisualLossFn: every active loss needs its label / target and confidence, one per row")
+        need = ctx.needs_input_grad[0]
+        ws = torch.empty(int(L.vb_visual_loss_ws_floats(M)), dtype=torch.float32, device=dev)
+        losses = torch.empty(4, dtype=torch.float32, device=dev)
+        check(L.vb_visual_loss_fwd_bwd(_lib.dtype_code(scores.dtype), ptr(scores), _ld(scores), n_obj, n_attr, n_feat,
+                                       ptr(ol) if n_obj > 0 else None, ptr(oc) if n_obj > 0 else None,
+                                       ptr(al) if n_attr > 0 else None, ptr(ac) if n_attr > 0 else None,
+                                       ptr(ft), n_feat, ptr(fc) if n_feat > 0 else None,
+                                       float(w_obj), float(w_attr), float(w_feat), ptr(ws), ptr(losses),
+                                       ptr(scores) if need else None, _ld(scores), M, stream_ptr()), "vb_visual_loss_fwd_bwd")
+        ctx.widths = (n_obj, n_attr, n_feat)
+        if need:
+            producer = scores.grad_fn
+            ctx.producer = producer if getattr(producer, "_vb_takes_alpha", False) else None
+            ctx.dscores = scores.detach()
+        return losses
+
+    @staticmethod
+    def backward(ctx, dl):
+        g = ctx.dscores
+        a = (dl[:3] + dl[3]).to(torch.float32).contiguous()          # per-segment upstream scalars, on the device
+        if ctx.producer is not None:
+            ctx.producer._vb_alpha = a
+        else:
+            g = g.clone()                                            # the stored gradient stays that of an upstream 1
+            off = 0
+            for k, n in enumerate(ctx.widths):
+                if n:
+                    g[:, off:off + n].mul_(a[k].to(g.dtype))
+                off += n
+        return (g,) + (None,) * 12
