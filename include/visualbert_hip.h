@@ -278,6 +278,38 @@ int vb_visual_loss_fwd_bwd(int dtype, const void* scores, int64_t ld_scores, int
                            float w_obj, float w_attr, float w_feat, float* ws, float* losses,
                            void* dscores, int64_t ld_dscores, int M, void* stream);
 
+/* The answer head of the sibling LXRT model: GELU + LayerNorm over WIDE rows, and the VQA / GQA fine-tuning loss.
+ * vb_ln_wide_fwd: g = act ? gelu(x) : x (act = VB_ACT_GELU / VB_ACT_NONE; BERT's erf form), y = gamma * (g - mean) / sqrt(var + eps)
+ *   + beta.  x, y: T [M, H] contiguous (T = fp32 or bf16 by dtype); mean, rstd: fp32 [M] (written; statistics in fp32, biased
+ *   variance, two passes -- mean, then the centred second moment --, eps inside the sqrt, as vb_ln_fwd); gamma, beta: fp32 [H].
+ *   8 <= H <= 8192, H % 8 == 0 (vb_ln_fwd stops at 1024; the small widths are taken too, so that a head has one code path).
+ *   One 256-thread workgroup per row, the row in registers.  VB_ERR_ARG for a NULL pointer, M <= 0, another H or another act.
+ * vb_ln_wide_bwd: x is the pre-activation the forward read; g and x-hat are recomputed from x, mean, rstd.  dx (T [M, H], may
+ *   alias dy) = d / dx through the LayerNorm and, with act, through GELU' -- the activation never exists in memory and there is no
+ *   separate activation-backward launch.  dgamma / dbeta: fp32 [H], ACCUMULATED (the vb_ln_bwd contract), either may be NULL.
+ *   ws: fp32 [vb_ln_wide_bwd_ws_floats(M, H)], required, need not be zeroed: per-workgroup partial column sums, added by a second
+ *   launch in a fixed order -- no float atomics, the same bits from run to run.
+ * Replaces GeLU() + BertLayerNorm(hid_dim * 2) of BertVisualAnswerHead.logit_fc (unsupervised_visualbert/src/lxrt/modeling.py:
+ * 960-965; the same lines are VQAModel.logit_fc, src/tasks/vqa_model.py:28-34) and autograd. */
+int vb_ln_wide_fwd(int dtype, const void* x, int act, void* y, float* mean, float* rstd,
+                   const float* gamma, const float* beta, int M, int H, float eps, void* stream);
+int64_t vb_ln_wide_bwd_ws_floats(int M, int H);
+int vb_ln_wide_bwd(int dtype, const void* dy, const void* x, int act, const float* mean, const float* rstd,
+                   const float* gamma, void* dx, float* dgamma, float* dbeta, float* ws,
+                   int M, int H, void* stream);
+/* vb_bce_logits_fwd_bwd: BCEWithLogitsLoss()(logits, target) * V on soft targets in [0, 1]:
+ *   loss[0] = (1 / M) sum_r sum_v [max(x, 0) - x t + log1p(exp(-|x|))] -- the form that stays finite at x = +-90.
+ *   logits, target: fp32 [M, V] with leading dimensions (pad columns are ignored).  dlogits (fp32 [M, ld_dlogits], may be NULL):
+ *   (sigmoid(x) - t) / M for an upstream gradient of 1, pad columns up to ld_dlogits zeroed (the vb_ce_fwd_bwd contract).
+ *   score[0] (may be NULL): the mean over rows of target[r, argmax_v logits[r, v]], the lowest index on ties.
+ *   ws: fp32 [vb_bce_logits_ws_floats(M)], required, need not be zeroed: every row stores its loss term and its score there and a
+ *   second single-workgroup launch adds them as a fixed tree (no float atomics): bit-identical from run to run.
+ * Replaces src/tasks/vqa.py:72, :106-107 (the loss), :114-117 (the accuracy read off the argmax) and autograd. */
+int64_t vb_bce_logits_ws_floats(int M);
+int vb_bce_logits_fwd_bwd(const float* logits, int64_t ld_logits, const float* target, int64_t ld_target,
+                          float* ws, float* loss, float* score, float* dlogits, int64_t ld_dlogits,
+                          int M, int V, void* stream);
+
 /* Heads with a tiny output width (seq_relationship 768->2, modeling.py:451; NLVR2 768->2, :1558).
  * x: T [M,K]; W: fp32 master [N,K]; y / dy: fp32 [M,N].  Backward: dx (T, overwritten, may be NULL),
  * dW / db fp32 ACCUMULATED (may be NULL); scale_dev: optional fp32 device scalar (upstream gradient). */

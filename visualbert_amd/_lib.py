@@ -50,6 +50,11 @@ SIGNATURES = {
     "vb_kldiv_fwd_bwd": (_i, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i, _i, _p]),
     "vb_visual_loss_ws_floats": (_i64, [_i]),
     "vb_visual_loss_fwd_bwd": (_i, [_i, _p, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _i64, _p, _f, _f, _f, _p, _p, _p, _i64, _i, _p]),
+    "vb_ln_wide_fwd": (_i, [_i, _p, _i, _p, _p, _p, _p, _p, _i, _i, _f, _p]),
+    "vb_ln_wide_bwd_ws_floats": (_i64, [_i, _i]),
+    "vb_ln_wide_bwd": (_i, [_i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
+    "vb_bce_logits_ws_floats": (_i64, [_i]),
+    "vb_bce_logits_fwd_bwd": (_i, [_p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _i, _i, _p]),
     "vb_small_linear_fwd": (_i, [_i, _p, _i64, _p, _p, _p, _i, _i, _i, _p]),
     "vb_small_linear_bwd": (_i, [_i, _p, _p, _i64, _p, _p, _i64, _p, _p, _p, _i, _i, _i, _p]),
     "vb_bert_adam_step": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p, _p, _f, _f, _f, _f, _f, _f, _f, _f, _i, _p]),

@@ -26,7 +26,11 @@ class against that forward run on the reference's own blocks (the golden generat
   LXRTPretrainingHeads                  :1297-1420 the heads of LXRTPretraining (`cls`, `obj_predict_head`) and its loss lines:
                                                    masked LM, image-text match and the masked-region objective -- object class,
                                                    attribute class, feature regression per region, each weighted by a per-region
-                                                   confidence / mask -- through ops.VisualLossFn (vb_visual_loss_fwd_bwd)"""
+                                                   confidence / mask -- through ops.VisualLossFn (vb_visual_loss_fwd_bwd)
+  BertVisualAnswerHead                  :956-969   Linear(H, 2H) -> GeLU -> LayerNorm(2H) -> Linear(2H, num_answers): GELU +
+                                                   LayerNorm in one kernel over the wide rows (ops.WideLayerNormFn), the VQA /
+                                                   GQA fine-tuning loss on its fp32 logits (ops.BCELogitsLossFn)
+  LXRTPretrainingHeadsQA                :1327-1436 LXRTPretrainingHeads + `answer_head` and the `qa` term (task_qa)"""
 import torch
 from torch import nn
 
@@ -347,8 +351,9 @@ class LXRTPretrainingHeads(nn.Module):
     and names: "Masked LM", "Matches", then the keys of visual_losses.  obj_labels: {key: (label, mask_conf)} -- int class ids
     [B, R] for obj / attr, the fp32 target feature [B, R, D] for feat, one confidence / mask per region.  Every visual term is
     (loss_r * mask_conf_r).mean() * loss_weight (the reference's 1 / 0.15; its `weight_disable` is loss_weight=1.0).
-    Not offered (NotImplementedError, never silently different): the QA answer head (its LayerNorm is 2 H wide, beyond the
-    LayerNorm kernels), the tag / symbolic heads, lxmert_style_nlvr and the `kl` loss form."""
+    The QA answer head (`task_qa`) is the subclass LXRTPretrainingHeadsQA, not a switch of this class.
+    Not offered (NotImplementedError, never silently different): the tag / symbolic heads, lxmert_style_nlvr and the `kl`
+    loss form."""
 
     def __init__(self, config, word_embedding_weight, task_mask_lm=True, task_matched=True, task_obj_predict=True,
                  visual_losses="obj,attr,feat", loss_weight=1 / 0.15, sizes=None, task_qa=False,
@@ -356,7 +361,8 @@ class LXRTPretrainingHeads(nn.Module):
         super(LXRTPretrainingHeads, self).__init__()
         from .modeling import BertPreTrainingHeads
         if task_qa:
-            raise NotImplementedError("task_qa: the answer head's LayerNorm is 2 x hidden_size wide, beyond the LayerNorm kernels")
+            raise NotImplementedError("task_qa: the answer head and its `qa` term are LXRTPretrainingHeadsQA(config, "
+                                      "word_embedding_weight, num_answers, ...), a subclass of this class")
         if use_tag_symbolic_embedding:
             raise NotImplementedError("use_tag_symbolic_embedding: the tag / symbolic heads are not implemented")
         if lxmert_style_nlvr:
@@ -373,6 +379,17 @@ class LXRTPretrainingHeads(nn.Module):
             self.obj_predict_head = BertVisualObjHead(config, visual_losses, sizes=sizes)
 
     def forward(self, lang_output, pooled_output, visn_output, masked_lm_labels=None, matched_label=None, obj_labels=None):
+        return self._finish(*self._terms(lang_output, pooled_output, visn_output, masked_lm_labels, matched_label, obj_labels),
+                            lang_output if lang_output is not None else visn_output)
+
+    @staticmethod
+    def _finish(total_loss, losses, losses_dict, like):
+        if total_loss is None:
+            total_loss = torch.zeros((), device=like.device)
+        return total_loss, torch.stack(losses).unsqueeze(0) if losses else torch.zeros((1, 0)), losses_dict
+
+    def _terms(self, lang_output, pooled_output, visn_output, masked_lm_labels, matched_label, obj_labels):
+        """(total_loss or None, [terms, detached], {name: term, detached}) in the reference's order"""
         total_loss = None
         losses, losses_dict = [], {}
 
@@ -403,9 +420,82 @@ class LXRTPretrainingHeads(nn.Module):
             visn = ops.VisualLossFn.apply(scores, n_obj, n_attr, n_feat, *args, w, w, w)
             for k in self.visual_losses:
                 add(k, visn[ops.VISUAL_SEGMENTS.index(k)])
-        if total_loss is None:
-            total_loss = torch.zeros((), device=lang_output.device if lang_output is not None else visn_output.device)
-        return total_loss, torch.stack(losses).unsqueeze(0) if losses else torch.zeros((1, 0)), losses_dict
+        return total_loss, losses, losses_dict
+
+
+class GeLU(nn.Module):
+    """lxrt/modeling.py:121-131: index 1 of BertVisualAnswerHead.logit_fc, parameter-free.  It holds the reference's place in the
+    nn.Sequential (so that the state-dict keys are logit_fc.0 / .2 / .3); the head applies it inside the LayerNorm kernel."""
+
+    def forward(self, x):
+        raise RuntimeError("visualbert_amd: GeLU is fused into the LayerNorm behind it (ops.WideLayerNormFn); call the head")
+
+
+class BertVisualAnswerHead(nn.Module):
+    """lxrt/modeling.py:956-969, same state-dict keys: logit_fc = Sequential(Linear(H, 2H), GeLU, BertLayerNorm(2H),
+    Linear(2H, num_answers)) -- the `task_qa` head of LXRTPretraining and, verbatim, VQAModel.logit_fc / GQAModel.logit_fc
+    (src/tasks/vqa_model.py:28-34).  A plain GEMM for logit_fc.0, GELU + LayerNorm in one kernel over the 2H-wide rows
+    (ops.WideLayerNormFn), a GEMM to fp32 logits.
+
+    forward(pooled)              -> logits fp32 [.., num_answers]
+    forward(pooled, target=t)    -> (logits, loss, score): BCEWithLogitsLoss()(logits, t) * num_answers on soft targets t
+                                    [B, num_answers] and the mean VQA score of the argmax (src/tasks/vqa.py:72, :106-107, :114-117)
+    forward(pooled, labels=ans)  -> (logits, loss): CrossEntropyLoss(ignore_index=-1), the pre-training `qa` term (:1423-1436)"""
+
+    def __init__(self, config, num_answers):
+        super(BertVisualAnswerHead, self).__init__()
+        hid_dim = config.hidden_size
+        if hid_dim % 4 or not 8 <= hid_dim * 2 <= 8192:
+            raise NotImplementedError("hidden_size %d: the wide LayerNorm kernel takes 2 x hidden_size in 8 .. 8192, a multiple of 8"
+                                      % hid_dim)
+        self.num_answers = int(num_answers)
+        self.logit_fc = nn.Sequential(
+            nn.Linear(hid_dim, hid_dim * 2),
+            GeLU(),
+            BertLayerNorm(hid_dim * 2, eps=1e-12),
+            nn.Linear(hid_dim * 2, self.num_answers),
+        )
+
+    def forward(self, hidden_states, target=None, labels=None):
+        fc0, ln, fc3 = self.logit_fc[0], self.logit_fc[2], self.logit_fc[3]
+        h = ops.LinearFn.apply(hidden_states, fc0.weight, fc0.bias, None, False)
+        h = ops.WideLayerNormFn.apply(h, ln.weight, ln.bias, ln.variance_epsilon, "gelu")
+        if target is not None and labels is not None:
+            raise ValueError("BertVisualAnswerHead: soft targets (the VQA loss) or class labels (the pre-training term), not both")
+        if target is not None:
+            return ops.BCELogitsLossFn.apply(h, target, fc3.weight, fc3.bias)
+        if labels is not None:
+            return ops.AnswerCELossFn.apply(h, labels, fc3.weight, fc3.bias)
+        return ops.LinearFn.apply(h, fc3.weight, fc3.bias, None, True)
+
+
+class LXRTPretrainingHeadsQA(LXRTPretrainingHeads):
+    """LXRTPretrainingHeads with `task_qa` (lxrt/modeling.py:1327-1328, :1361-1362, :1423-1436): `answer_head`
+    (BertVisualAnswerHead over the pooled output) and the `qa` term, CrossEntropyLoss(ignore_index=-1) of the answer scores
+    against `ans`, placed after the visual terms.  forward returns the reference's four values
+    (total_loss, losses [1, n], answer_score.detach(), losses_dict); without `ans` the head still runs and no term is added."""
+
+    def __init__(self, config, word_embedding_weight, num_answers, **kwargs):
+        if kwargs.pop("task_qa", True) is not True:
+            raise ValueError("LXRTPretrainingHeadsQA is the task_qa form; use LXRTPretrainingHeads without it")
+        super(LXRTPretrainingHeadsQA, self).__init__(config, word_embedding_weight, **kwargs)
+        self.task_qa = True
+        self.num_answers = int(num_answers)
+        self.answer_head = BertVisualAnswerHead(config, self.num_answers)
+
+    def forward(self, lang_output, pooled_output, visn_output, masked_lm_labels=None, matched_label=None, obj_labels=None,
+                ans=None):
+        total_loss, losses, losses_dict = self._terms(lang_output, pooled_output, visn_output, masked_lm_labels, matched_label,
+                                                      obj_labels)
+        if ans is not None:
+            answer_score, answer_loss = self.answer_head(pooled_output, labels=ans.reshape(-1))
+            total_loss = answer_loss if total_loss is None else total_loss + answer_loss
+            losses.append(answer_loss.detach())
+            losses_dict["qa"] = answer_loss.detach()
+        else:
+            answer_score = self.answer_head(pooled_output)
+        total_loss, losses, losses_dict = self._finish(total_loss, losses, losses_dict, pooled_output)
+        return total_loss, losses, answer_score.detach(), losses_dict
 
 
 def lxrt_init_weights(module, initializer_range=0.02):

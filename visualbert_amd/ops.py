@@ -1850,3 +1850,141 @@ class VisualLossFn(torch.autograd.Function):
                     g[:, off:off + n].mul_(a[k].to(g.dtype))
                 off += n
         return (g,) + (None,) * 12
+
+
+# ------------------------------------------------------------------------------------------------
+# the answer head of the sibling LXRT model (lxrt.BertVisualAnswerHead): GELU + LayerNorm over 2 H columns, BCE / CE on fp32 logits
+# ------------------------------------------------------------------------------------------------
+@x3_aware
+class WideLayerNormFn(torch.autograd.Function):
+    """y = LN(act(x)) over rows of 8 .. 8192 columns (vb_ln_wide_fwd / vb_ln_wide_bwd) -- GeLU() + BertLayerNorm(hid_dim * 2) of
+    BertVisualAnswerHead.logit_fc (unsupervised_visualbert/src/lxrt/modeling.py:960-965).  act: None / "gelu".  x is the
+    pre-activation; the activation itself is never stored: the backward rebuilds it from x."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, act):
+        x2 = as2d(x).contiguous()
+        M, H = x2.shape
+        y = torch.empty((M, H), dtype=x2.dtype, device=x2.device)
+        mean = torch.empty(M, dtype=torch.float32, device=x2.device)
+        rstd = torch.empty(M, dtype=torch.float32, device=x2.device)
+        code = _ACT[act]
+        check(_lib.lib().vb_ln_wide_fwd(_lib.dtype_code(x2.dtype), ptr(x2), code, ptr(y), ptr(mean), ptr(rstd), ptr(gamma.detach()),
+                                        ptr(beta.detach()), M, H, float(eps), stream_ptr()), "vb_ln_wide_fwd")
+        ctx.act = code
+        ctx.gamma, ctx.beta = gamma, beta
+        ctx.save_for_backward(x2, mean, rstd)
+        return y.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, mean, rstd = ctx.saved_tensors
+        M, H = x2.shape
+        dy2 = as2d(dy)
+        if dy2.dtype != x2.dtype:
+            dy2 = dy2.to(x2.dtype)
+        dy2 = dy2.contiguous()
+        gg, dg = grad_target(ctx.gamma)
+        gb, db = grad_target(ctx.beta)
+        L = _lib.lib()
+        dx = torch.empty_like(x2)
+        ws = torch.empty(int(L.vb_ln_wide_bwd_ws_floats(M, H)), dtype=torch.float32, device=x2.device)
+        check(L.vb_ln_wide_bwd(_lib.dtype_code(x2.dtype), ptr(dy2), ptr(x2), ctx.act, ptr(mean), ptr(rstd), ptr(ctx.gamma.detach()),
+                               ptr(dx), ptr(gg), ptr(gb), ptr(ws), M, H, stream_ptr()), "vb_ln_wide_bwd")
+        return dx.view(dy.shape), grad_result(gg, dg), grad_result(gb, db), None, None
+
+
+def _answer_logits_bwd(ctx, dloss):
+    """the backward both answer losses share: the stored d loss / d logits (upstream 1) times the upstream scalar, through the Linear"""
+    x2, dlogits = ctx.saved_tensors                    # dlogits: the whole fp32 [M, ld] buffer, pad columns zeroed by the loss kernel
+    if dlogits is None:
+        raise RuntimeError("visualbert_amd: backward through the answer head's loss needs a target")
+    weight, bias = ctx.wb
+    M, N = dlogits.size(0), weight.size(0)
+    dt = x2.dtype
+    up = _upstream_scalar(dloss)
+    dl = torch.empty(dlogits.shape, dtype=dt, device=x2.device)
+    if up is None:
+        dl.copy_(dlogits)
+    else:
+        torch.mul(dlogits, up, out=dl)                  # scale, cast and the zero pad columns in one pass
+    if dl.size(1) != N:
+        dl = dl[:, :N]
+    gw, d1 = grad_target(weight)
+    gb, d2 = grad_target(bias)
+    linear_wgrad(dl, x2, gw)
+    colsum(dl, gb)
+    dx = linear_dgrad(dl, weight_for(weight, dt)).reshape(ctx.x_shape) if ctx.needs_input_grad[0] else None
+    return dx, grad_result(gw, d1), grad_result(gb, d2)
+
+
+def _answer_logits_fwd(ctx, x, weight, bias):
+    x2 = as2d(x)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    logits = linear_fwd(x2, weight_for(weight, x2.dtype), bias.detach(), out_dtype=torch.float32)
+    ctx.wb = (weight, bias)
+    ctx.x_shape = x.shape
+    return x2, logits
+
+
+@x3_aware
+class BCELogitsLossFn(torch.autograd.Function):
+    """Linear(K -> num_answers) with fp32 logits + BCEWithLogitsLoss()(logits, target) * num_answers on soft targets + the VQA
+    score (vb_bce_logits_fwd_bwd): the last Linear of VQAModel.logit_fc and the loss / accuracy lines of
+    unsupervised_visualbert/src/tasks/vqa.py:72, :106-107, :114-117.  Returns (logits fp32 [M, num_answers], loss, score);
+    target None: the logits alone (loss and score 0, no backward)."""
+
+    @staticmethod
+    def forward(ctx, x, target, weight, bias):
+        x2, logits = _answer_logits_fwd(ctx, x, weight, bias)
+        M, N = logits.shape
+        dev = x2.device
+        loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        score = torch.zeros(1, dtype=torch.float32, device=dev)
+        dlogits = None
+        if target is not None:
+            L = _lib.lib()
+            tg = target.reshape(M, N).to(torch.float32).contiguous()
+            dlogits = torch.empty((M, round_up(N, 8)), dtype=torch.float32, device=dev)       # the kernel zeroes the pad columns
+            ws = torch.empty(int(L.vb_bce_logits_ws_floats(M)), dtype=torch.float32, device=dev)
+            check(L.vb_bce_logits_fwd_bwd(ptr(logits), _ld(logits), ptr(tg), tg.stride(0), ptr(ws), ptr(loss), ptr(score),
+                                          ptr(dlogits), dlogits.size(1), M, N, stream_ptr()), "vb_bce_logits_fwd_bwd")
+        ctx.save_for_backward(x2, dlogits)
+        ctx.mark_non_differentiable(logits)
+        ctx.set_materialize_grads(False)
+        return logits, loss.reshape(()), score.reshape(())
+
+    @staticmethod
+    def backward(ctx, _dl, dloss, _ds):
+        dx, gw, gb = _answer_logits_bwd(ctx, dloss)
+        return dx, None, gw, gb
+
+
+@x3_aware
+class AnswerCELossFn(torch.autograd.Function):
+    """The same Linear + CrossEntropyLoss(ignore_index=-1) over the answer vocabulary (vb_ce_fwd_bwd on the fp32 logits): the
+    `qa` term of LXRTPretraining.forward (unsupervised_visualbert/src/lxrt/modeling.py:1423-1436).  Returns (logits, loss)."""
+
+    @staticmethod
+    def forward(ctx, x, labels, weight, bias):
+        x2, logits = _answer_logits_fwd(ctx, x, weight, bias)
+        M, N = logits.shape
+        dev = x2.device
+        lab = labels.reshape(-1).to(torch.int64).contiguous()
+        if lab.numel() != M:
+            raise RuntimeError("visualbert_amd.AnswerCELossFn: %d labels for %d rows" % (lab.numel(), M))
+        acc = torch.empty(66, dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        dlogits = torch.empty((M, round_up(N, 8)), dtype=torch.float32, device=dev)           # the kernel zeroes the pad columns
+        check(_lib.lib().vb_ce_fwd_bwd(_lib.VB_F32, ptr(logits), _ld(logits), ptr(lab), -1, ptr(acc), ptr(loss), ptr(dlogits),
+                                       dlogits.size(1), M, N, stream_ptr()), "vb_ce_fwd_bwd")
+        ctx.save_for_backward(x2, dlogits)
+        ctx.mark_non_differentiable(logits)
+        ctx.set_materialize_grads(False)
+        return logits, loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, _dl, dloss):
+        dx, gw, gb = _answer_logits_bwd(ctx, dloss)
+        return dx, None, gw, gb
